@@ -39,6 +39,44 @@ def log(msg):
           flush=True)
 
 
+# --dump-outputs writes at most this much in all (float32 samples)
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy, float32 (float64
+    for 32/64-bit integers and float64).
+
+    Every array gets the same share of DUMP_BUDGET_BYTES; one that is
+    bigger is sampled at sorted indices drawn from a generator seeded
+    by its name, so two runs (or two builds) pick the same elements.
+    Integer and float32/64 tensors are written by value; 16-bit floats
+    as their int16 bit patterns (see --dump-outputs)."""
+    import re
+    import zlib
+
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    per = max(DUMP_BUDGET_BYTES // 8 // max(len(arrays), 1), 1)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        flat = t.reshape(-1)
+        if flat.dtype in (torch.bfloat16, torch.float16):
+            flat = flat.view(torch.int16)
+        if flat.numel() > per:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(flat.numel(), (per,), generator=g)
+            flat = flat[idx.sort().values.to(flat.device)]
+        wide = flat.dtype in (torch.float64, torch.int32, torch.int64)
+        a = flat.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(
+            out_dir, re.sub(r"[^A-Za-z0-9._-]", "_", name) + ".npy"), a)
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 class _FanoutResult:
     """Minimal result shim for fan-out steps (log fields only)."""
 
@@ -118,7 +156,22 @@ def main():
                          "bigger than the box's disk, e.g. llama3-70b; "
                          "payloads are patterned bytes, so tensor-view "
                          "materialization is skipped")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last "
+                         "timed step handed its caller as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of at most "
+                         f"{DUMP_BUDGET_BYTES >> 20} MB in all).  16-bit "
+                         "float tensors are written as their bit patterns "
+                         "(exact in float32): the synthetic payload is "
+                         "arbitrary bytes, so their values include NaNs, "
+                         "which never compare equal")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that the "
+                         "headline figure does not need (none today: a "
+                         "plain run already does only setup, warmup, the "
+                         "timed steps and the result line)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -298,7 +351,13 @@ def main():
                     device=dev)
             scatter_targets[f.name] = (tg)
 
-    def dp_step(record_digests=False):
+    def _digests_u8(raw):
+        return torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+
+    # every step function takes keep=None or a dict: given a dict (the
+    # last timed step under --dump-outputs) it files what it hands its
+    # caller there, name -> tensor, and leaves those buffers alive
+    def dp_step(record_digests=False, keep=None):
         from demodel_amd.engine.formats import safetensors as st
         from demodel_amd.engine.loader import load_into
 
@@ -326,14 +385,28 @@ def main():
                     hdr = st.parse_header(f.blob.head)
                     n_t += len(load_into(f.blob, hdr, tg))
             t_sc2 = time.perf_counter()
-            n_t += len(res.tensors())
+            views = res.tensors()
+            n_t += len(views)
             log(f"scatter {t_sc2 - t_sc:.3f}s views "
                 f"{time.perf_counter() - t_sc2:.3f}s")
         if have_gpu:
             torch.cuda.synchronize()
+        if keep is not None:
+            for f in res.files:
+                if f.blob.digest_blob:
+                    keep["digests." + f.name] = _digests_u8(
+                        f.blob.digest_blob)
+                if args.virtual:
+                    keep["blob." + f.name] = f.blob.torch_u8()
+            if not args.virtual:
+                for n, t in views.items():
+                    keep["view." + n] = t
+                for tg in scatter_targets.values():
+                    for n, t in tg.items():
+                        keep["scatter." + n] = t
         return res, n_t
 
-    def gguf_step(record_digests=False):
+    def gguf_step(record_digests=False, keep=None):
         """Ollama-style pull (config 4): land the q4_K GGUF blob, then
         dequant EVERY quant tensor to bf16 on-GPU; ready = bf16 weights
         resident."""
@@ -360,20 +433,29 @@ def main():
             n_t = len(tensors)
             log(f"dequant overlap: {pd.launched_early}/{n_t} tensors "
                 f"launched before pull completion")
+            if keep is not None:
+                for n, t in tensors.items():
+                    keep["dequant." + n] = t
             del tensors
-            pd.recycle_arena()  # views dropped; reuse at 70B scale
+            if keep is None:
+                pd.recycle_arena()  # views dropped; reuse at 70B scale
             del pd
         else:
             gg = gguf.parse(blob)
             out_bytes = sum(t.n_elems * 2 for t in gg.tensors
                             if t.type_id in gguf.ProgressiveDequant.QUANT_IDS)
             n_t = len(gg.tensors)
+            if keep is not None:
+                keep["blob." + res.files[0].name] = blob.torch_u8()
+        if keep is not None and blob.digest_blob:
+            keep["digests." + res.files[0].name] = _digests_u8(
+                blob.digest_blob)
         if have_gpu:
             torch.cuda.synchronize()
         res.meta["dequant_bf16_bytes"] = out_bytes
         return res, n_t
 
-    def _stream_step(record_digests, patterns):
+    def _stream_step(record_digests, patterns, keep=None):
         """config 5 via the user-facing stream_dataset API: each landed
         shard's GPU decompression overlaps with the remaining pulls;
         counts DECOMPRESSED bytes landed in HBM rings."""
@@ -394,21 +476,23 @@ def main():
                                 eager=False):
             out_bytes += int(b.data.numel())
             n += 1
+            if keep is not None:
+                keep["shard." + b.name] = b.data
             del b
         if have_gpu:
             torch.cuda.synchronize()
         return _FanoutResult(out_bytes, time.perf_counter() - t0), n
 
-    def parquet_step(record_digests=False):
-        return _stream_step(record_digests, ("*.parquet",))
+    def parquet_step(record_digests=False, keep=None):
+        return _stream_step(record_digests, ("*.parquet",), keep)
 
-    def dataset_step(record_digests=False):
-        return _stream_step(record_digests, ("*.zst", "*.idx.json"))
+    def dataset_step(record_digests=False, keep=None):
+        return _stream_step(record_digests, ("*.zst", "*.idx.json"), keep)
 
     file_sizes = [(n, os.path.getsize(p) if p else sizes[n])
                   for n, p in sorted(files.items())]
 
-    def fanout_step(record_digests=False):
+    def fanout_step(record_digests=False, keep=None):
         """shard/broadcast modes: every rank ends with the full model."""
         from demodel_amd.engine.pull import _pull_blob
         from demodel_amd.parallel.fanout import (shard_assignment,
@@ -439,11 +523,14 @@ def main():
         assert got == total_bytes, (got, total_bytes)
         if have_gpu:
             torch.cuda.synchronize()
+        if keep is not None:
+            for n, t in out.items():
+                keep["blob." + n] = t
         return out
 
     step_bytes = total_bytes  # may be overridden by workloads below
 
-    def allgather_step(record_digests=False):
+    def allgather_step(record_digests=False, keep=None):
         """R2: every rank pulls 1/N of the concatenated manifest bytes
         via HTTP Range, reassembly by bucketed all-gather overlapped
         with the remaining download."""
@@ -503,25 +590,27 @@ def main():
         assert full.numel() >= total_bytes
         if have_gpu:
             torch.cuda.synchronize()
+        if keep is not None:
+            keep["allgather"] = full[:total_bytes]
         return _FanoutResult(total_bytes * world), 0
 
-    def one_step(record_digests=False):
+    def one_step(record_digests=False, keep=None):
         nonlocal step_bytes
         if args.model.startswith("gguf"):
-            return gguf_step(record_digests)
+            return gguf_step(record_digests, keep)
         if args.model == "dataset":
-            res, n = dataset_step(record_digests)
+            res, n = dataset_step(record_digests, keep)
             step_bytes = res.total_bytes
             return res, n
         if args.model == "parquet":
-            res, n = parquet_step(record_digests)
+            res, n = parquet_step(record_digests, keep)
             step_bytes = res.total_bytes
             return res, n
         if args.mode == "dp":
-            return dp_step(record_digests)
+            return dp_step(record_digests, keep)
         if args.mode == "allgather":
-            return allgather_step(record_digests)
-        res = fanout_step(record_digests)
+            return allgather_step(record_digests, keep)
+        res = fanout_step(record_digests, keep)
         return _FanoutResult(total_bytes * world), len(res)
 
     # warmup; the first pull records chunk digests so every TIMED pull is a
@@ -539,13 +628,25 @@ def main():
     sync()
     t0 = time.perf_counter()
     per_step = []
+    kept = {} if args.dump_outputs else None
+    last_res = None
     for i in range(args.steps):
-        res, _ = one_step()
+        last = kept is not None and i == args.steps - 1
+        res, _ = one_step(keep=kept if last else None)
         per_step.append(res.seconds_to_ready)
-        landers.recycle(res)
+        if last:
+            last_res = res  # its buffers back the kept arrays
+        else:
+            landers.recycle(res)
         del res
     sync()
     elapsed = time.perf_counter() - t0
+
+    if kept is not None:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(
+            args.dump_outputs, f"rank{rank}"), kept)
+        kept.clear()
+        del last_res
 
     if dist:
         et = torch.tensor([elapsed])

@@ -9,6 +9,15 @@ from demodel_amd.proxy.server import ProxyServer
 from demodel_amd.testing.origin import FakeOrigin
 
 
+def host_landers(**kw):
+    """A LanderPool that lands in host memory whether or not the machine
+    has a GPU: tests of the CPU landing target pass it as `landers=` so
+    that they check the same path everywhere."""
+    from demodel_amd.engine.pull import LanderPool
+
+    return LanderPool(0, gpu=False, **kw)
+
+
 class LoopThread:
     def __init__(self):
         self.loop = asyncio.new_event_loop()

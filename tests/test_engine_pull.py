@@ -14,7 +14,7 @@ from demodel_amd.engine import pull as pull_mod
 from demodel_amd.engine.formats import gguf, safetensors as st
 from demodel_amd.engine.pipeline import (HostLander, _compress,
                                          _host_sha256_finish)
-from helpers import Stack
+from helpers import Stack, host_landers
 
 
 # ---------------------------------------------------------------- #
@@ -113,7 +113,8 @@ def test_pull_hf_end_to_end(stack, tmp_path):
     })
     res = pull_mod.pull_hf("org/tiny", endpoint=stack.origin_base,
                            verify="digest", workers=2,
-                           out_dir=str(tmp_path / "out"))
+                           out_dir=str(tmp_path / "out"),
+                           landers=host_landers())
     assert res.total_bytes == sum(
         os.path.getsize(tmp_path / f)
         for f in ("model.safetensors", "config.json"))
@@ -228,7 +229,7 @@ def test_recycle_noop_on_cpu(stack, tmp_path):
     p = tmp_path / "c.bin"
     p.write_bytes(data)
     stack.origin.add_hf_repo("org/cyc", {"c.bin": str(p)})
-    landers = pull_mod.LanderPool(0)
+    landers = host_landers()
     res = pull_mod.pull_hf("org/cyc", endpoint=stack.origin_base,
                            verify="chunked", workers=1, landers=landers)
     assert landers.recycle(res) == 0  # host blobs are not pooled
@@ -242,7 +243,7 @@ def test_pull_hf_dataset_repo_type(stack, tmp_path):
     stack.origin.add_hf_repo("org/dset", {"shard.bin": str(p)})
     res = pull_mod.pull_hf("org/dset", endpoint=stack.origin_base,
                            verify="chunked", workers=1,
-                           repo_type="dataset")
+                           repo_type="dataset", landers=host_landers())
     f = res.files[0]
     assert f.url.endswith("/datasets/org/dset/resolve/main/shard.bin") \
         or "/datasets/org/dset/" in f.url or f.nbytes == len(data)
@@ -372,7 +373,7 @@ def test_gated_repo_token_flow(stack, tmp_path, monkeypatch):
     # origin 403s any /cdn request that carries it)
     monkeypatch.setenv("HF_TOKEN", "s3cret")
     res = pull_mod.pull_hf("org/gated", endpoint=stack.origin_base,
-                           workers=1)
+                           workers=1, landers=host_landers())
     f = [x for x in res.files if x.name == "g.bin"][0]
     assert bytes(f.blob.buffer) == data
     # and the CDN host really served it (cross-host redirect taken)
@@ -398,8 +399,15 @@ def test_gated_repo_resume_does_not_leak_token(stack, tmp_path,
     cdn_port = stack.lt.call(cdn.start())
     stack.origin.cdn_base = f"http://127.0.0.1:{cdn_port}"
     monkeypatch.setenv("HF_TOKEN", "tok")
+    # the resume under test is the streamed (whole-body GET) landing of
+    # a machine without a GPU; with one, a chunk-verified pull opens
+    # with a Range probe instead, so pin the engine to the former
+    import demodel_amd.gpu
+
+    monkeypatch.setattr(demodel_amd.gpu, "have_gpu", lambda: False)
     res = pull_mod.pull_hf("org/gres", endpoint=stack.origin_base,
-                           workers=1, slab_bytes=256 << 10)
+                           workers=1,
+                           landers=host_landers(slab_bytes=256 << 10))
     f = [x for x in res.files if x.name == "gr.bin"][0]
     assert bytes(f.blob.buffer) == data
     assert not cdn.drop_once  # the drop fired -> a resume happened

@@ -10,7 +10,7 @@ import pytest
 
 from demodel_amd.engine import pull as pull_mod
 from demodel_amd.engine.pipeline import DigestMismatch
-from helpers import Stack
+from helpers import Stack, host_landers
 
 
 @pytest.fixture()
@@ -63,7 +63,8 @@ def test_peer_digests_endpoint_and_verified_pull(stack, tmp_path):
 
     # peer-verified pull: engine compares every chunk to the record
     res = pull_mod.pull_hf("org/p", endpoint=stack.endpoint,
-                           verify="chunked", workers=1, peer_verify=True)
+                           verify="chunked", workers=1, peer_verify=True,
+                           landers=host_landers())
     f = res.files[0]
     assert f.blob.verify_chunk == 64 << 10
     assert bytes(f.blob.buffer) == data

@@ -8,7 +8,7 @@ import urllib.request
 import pytest
 
 from demodel_amd.engine import pull as pull_mod
-from helpers import Stack
+from helpers import Stack, host_landers
 
 
 @pytest.fixture()
@@ -30,7 +30,7 @@ def test_pull_resumes_after_drop(stack, tmp_path):
     # and the resume continues WITH a Range request
     res = pull_mod.pull_hf("org/r", endpoint=stack.origin_base,
                            verify="digest", workers=1,
-                           slab_bytes=256 << 10)
+                           landers=host_landers(slab_bytes=256 << 10))
     f = res.files[0]
     assert f.nbytes == len(data)
     assert f.blob.sha256 == hashlib.sha256(data).hexdigest()

@@ -4,7 +4,7 @@ second load offline from the cache."""
 
 import pytest
 
-from helpers import Stack
+from helpers import Stack, host_landers
 
 transformers = pytest.importorskip("transformers")
 
@@ -76,7 +76,8 @@ def test_pull_pretrained_cpu(tiny_gpt2_dir, tmp_path):
         stack.origin.add_hf_repo("tiny-random/gpt2", files)
         model, res = pull_pretrained("tiny-random/gpt2",
                                      endpoint=stack.origin_base,
-                                     workers=2)
+                                     workers=2, device="cpu",
+                                     landers=host_landers())
         assert res.total_bytes > 0
         ref = transformers.GPT2LMHeadModel.from_pretrained(
             str(tiny_gpt2_dir))
