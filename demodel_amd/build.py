@@ -75,13 +75,20 @@ HIP_SRCS = [
 ]
 
 
+# in-tree headers a source includes (rebuild triggers)
+HIP_HDRS = {
+    "hip_core.cpp": [os.path.join(CSRC, "resource_cache.h")],
+}
+
+
 def build_hip(force: bool = False) -> str:
     out = os.path.join(PKG_DIR, "_hip.so")
     srcs = [os.path.join(CSRC, s) for s in HIP_SRCS
             if os.path.exists(os.path.join(CSRC, s))]
     if not srcs:
         raise RuntimeError("no HIP sources present")
-    if not force and _newer(out, srcs):
+    hdrs = [p for ps in HIP_HDRS.values() for p in ps]
+    if not force and _newer(out, srcs + hdrs):
         return out
     hipcc = os.environ.get("HIPCC", "hipcc")
     objs = []
@@ -90,7 +97,7 @@ def build_hip(force: bool = False) -> str:
         obj = os.path.join(
             PKG_DIR, "_build", os.path.basename(src).rsplit(".", 1)[0] + ".o"
         )
-        if not _newer(obj, [src]):
+        if not _newer(obj, [src] + HIP_HDRS.get(os.path.basename(src), [])):
             cmd = (
                 [hipcc, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17",
                  "-fPIC", "-fvisibility=hidden", "-c", src, "-o", obj]

@@ -18,11 +18,14 @@
 #include <sys/types.h>
 #include <unistd.h>
 #include <cerrno>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "resource_cache.h"
 
 namespace py = pybind11;
 
@@ -150,53 +153,224 @@ class DeviceBuffer {
   std::shared_ptr<DeviceBufferImpl> impl_;
 };
 
+// ------------------------------------------------------------------------
+// Process-lifetime caches under PinnedPool / Stream / Event.
+//
+// hipHostMalloc of a ring (pin + map pages for the GPU) and stream/event
+// creation are driver round-trips that contend when every worker thread of
+// a pull does them at once; ring geometry does not change from pull to
+// pull, so the resources are parked here when their owner dies and handed
+// to the next owner of the same (device, size class).
+//
+// DEMODEL_PINNED_CACHE_MB caps the idle pinned bytes (default 4096; the
+// default geometry with workers=8 needs 16 rings x 4 x 32 MiB = 2 GiB, the
+// rest is room for the proxy's prefetch landers).  0 turns all three caches
+// off: every release frees, exactly as before the caches existed.
+
+static const uint64_t kSlabGranule = 2ull << 20;
+static const uint64_t kHandleCap = 4096;  // idle streams / events, each
+
+static uint64_t pinned_cap_from_env() {
+  uint64_t mb = 4096;
+  if (const char* v = getenv("DEMODEL_PINNED_CACHE_MB")) {
+    char* end = nullptr;
+    errno = 0;
+    unsigned long long x = strtoull(v, &end, 10);
+    if (end != v && errno == 0 && *v != '-') mb = x;
+  }
+  return mb << 20;
+}
+
+struct Caches {
+  demodel::ResourceCache<void*> pinned;
+  demodel::ResourceCache<hipStream_t> streams;
+  demodel::ResourceCache<hipEvent_t> events;
+  bool on;
+
+  explicit Caches(uint64_t cap)
+      : pinned(
+            [](int, uint64_t nbytes) {
+              void* p = nullptr;
+              HIP_CHECK(hipHostMalloc(&p, nbytes, 0));
+              return p;
+            },
+            [](int, uint64_t, void* p) { (void)hipHostFree(p); }, cap),
+        streams(
+            [](int, uint64_t prio) {
+              hipStream_t s = nullptr;
+              HIP_CHECK(hipStreamCreateWithPriority(
+                  &s, hipStreamNonBlocking, (int)(int64_t)prio));
+              return s;
+            },
+            [](int, uint64_t, hipStream_t s) { (void)hipStreamDestroy(s); },
+            cap ? kHandleCap : 0),
+        events(
+            [](int, uint64_t flags) {
+              hipEvent_t e = nullptr;
+              HIP_CHECK(hipEventCreateWithFlags(&e, (unsigned)flags));
+              return e;
+            },
+            [](int, uint64_t, hipEvent_t e) { (void)hipEventDestroy(e); },
+            cap ? kHandleCap : 0),
+        on(cap > 0) {}
+};
+
+// Leaked on purpose: the HIP runtime may already be torn down when static
+// destructors run, and the OS reclaims pinned memory at exit anyway.
+static Caches& caches() {
+  static Caches* c = new Caches(pinned_cap_from_env());
+  return *c;
+}
+
+// Pinned host slabs plus the landing ring that fences their reuse: each
+// slab has an event recorded after its H2D copy and a busy flag, so a slab
+// is refilled only once the GPU has read it.  One thread drives a ring (the
+// engine keeps one lander per worker thread); the caches below it are
+// thread-safe.
+//
+// Slabs go back to the cache in the destructor, never to hipHostFree while
+// the cache has room.  hipHostFree's implicit device synchronisation used
+// to guarantee that no copy still touched a slab; here the destructor
+// drains the ring's own fences, and synchronises the device when a raw
+// slab pointer was handed out (copies the ring did not see).  If any of
+// that fails the slabs are freed, not cached.
 class PinnedPool {
  public:
   PinnedPool(size_t slab_bytes, int n_slabs) : slab_bytes_(slab_bytes) {
-    slabs_.resize(n_slabs);
-    for (auto& s : slabs_) HIP_CHECK(hipHostMalloc(&s, slab_bytes, 0));
+    if (n_slabs < 0) throw std::invalid_argument("n_slabs < 0");
+    HIP_CHECK(hipGetDevice(&device_));
+    Caches& c = caches();
+    class_ = c.on ? demodel::round_up_size_class(slab_bytes, kSlabGranule)
+                  : slab_bytes;
+    try {
+      for (int i = 0; i < n_slabs; i++) {
+        slabs_.push_back(c.pinned.take(device_, class_, class_));
+        events_.push_back(
+            c.events.take(device_, hipEventDisableTiming, 1));
+      }
+    } catch (...) {
+      release_all(true);  // untouched so far
+      throw;
+    }
+    busy_.assign(n_slabs, 0);
   }
   ~PinnedPool() {
-    for (auto& s : slabs_)
-      if (s) hipHostFree(s);
+    bool clean = drain_quiet();
+    if (clean && raw_used_ && caches().on) {
+      int cur = -1;
+      clean = hipGetDevice(&cur) == hipSuccess && cur == device_ &&
+              hipDeviceSynchronize() == hipSuccess;
+    }
+    release_all(clean);
   }
+  PinnedPool(const PinnedPool&) = delete;
+  PinnedPool& operator=(const PinnedPool&) = delete;
+
   int n_slabs() const { return (int)slabs_.size(); }
   size_t slab_bytes() const { return slab_bytes_; }
-  uintptr_t slab_ptr(int i) const { return (uintptr_t)slabs_.at(i); }
+  uintptr_t slab_ptr(int i) {
+    raw_used_ = true;  // caller may queue copies the ring cannot fence
+    return (uintptr_t)slabs_.at(i);
+  }
   py::memoryview slab_view(int i) {
     return py::memoryview::from_memory(slabs_.at(i), slab_bytes_);
   }
 
+  // Wait until the GPU has read slot's previous contents.
+  void acquire(int slot) {
+    if (busy_.at(slot)) {
+      HIP_CHECK(hipEventSynchronize(events_[slot]));
+      busy_[slot] = 0;
+    }
+  }
+  // Queue slab[slot][0:nbytes) -> dst on stream and fence the slot.
+  void submit(int slot, uintptr_t dst, size_t nbytes, uintptr_t stream) {
+    void* src = slabs_.at(slot);
+    if (nbytes > slab_bytes_)
+      throw std::out_of_range("submit: nbytes exceeds the slab");
+    HIP_CHECK(hipMemcpyAsync((void*)dst, src, nbytes, hipMemcpyHostToDevice,
+                             (hipStream_t)stream));
+    busy_[slot] = 1;  // set first: a failed record must not hide the copy
+    HIP_CHECK(hipEventRecord(events_[slot], (hipStream_t)stream));
+  }
+  // Make `stream` wait for slot's last submitted copy.
+  void stream_wait(int slot, uintptr_t stream) {
+    HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, events_.at(slot), 0));
+  }
+  void drain() {
+    for (int i = 0; i < (int)busy_.size(); i++) acquire(i);
+  }
+
  private:
+  bool drain_quiet() {
+    bool ok = true;
+    for (size_t i = 0; i < busy_.size(); i++)
+      if (busy_[i] && hipEventSynchronize(events_[i]) != hipSuccess)
+        ok = false;
+    return ok;
+  }
+  void release_all(bool reusable) {
+    Caches& c = caches();
+    for (void* s : slabs_)
+      c.pinned.release(device_, class_, class_, s, reusable);
+    for (hipEvent_t e : events_)
+      c.events.release(device_, hipEventDisableTiming, 1, e, reusable);
+    slabs_.clear();
+    events_.clear();
+  }
+
   size_t slab_bytes_;
+  uint64_t class_ = 0;
+  int device_ = 0;
+  bool raw_used_ = false;
   std::vector<void*> slabs_;
+  std::vector<hipEvent_t> events_;
+  std::vector<char> busy_;
 };
 
 class Stream {
  public:
-  explicit Stream(int priority = 0) {
-    HIP_CHECK(hipStreamCreateWithPriority(&s_, hipStreamNonBlocking,
-                                          priority));
-    owned_ = true;
+  explicit Stream(int priority = 0)
+      : key_((uint64_t)(int64_t)priority) {
+    HIP_CHECK(hipGetDevice(&device_));
+    s_ = caches().streams.take(device_, key_, 1);
   }
   ~Stream() {
-    if (owned_ && s_) hipStreamDestroy(s_);
+    // cached only once idle; a stream that fails to synchronise is dropped
+    Caches& c = caches();
+    bool idle = c.on && hipStreamSynchronize(s_) == hipSuccess;
+    c.streams.release(device_, key_, 1, s_, idle);
   }
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
   void sync() { HIP_CHECK(hipStreamSynchronize(s_)); }
   uintptr_t handle() const { return (uintptr_t)s_; }
   hipStream_t raw() const { return s_; }
 
  private:
   hipStream_t s_ = nullptr;
-  bool owned_ = false;
+  uint64_t key_;
+  int device_ = 0;
 };
 
 class Event {
  public:
-  Event() { HIP_CHECK(hipEventCreate(&e_)); }
-  ~Event() {
-    if (e_) hipEventDestroy(e_);
+  // timing=false (hipEventDisableTiming) for pure fences; elapsed_ms needs
+  // both events created with timing.
+  explicit Event(bool timing = true)
+      : flags_(timing ? hipEventDefault : hipEventDisableTiming) {
+    HIP_CHECK(hipGetDevice(&device_));
+    e_ = caches().events.take(device_, flags_, 1);
   }
+  ~Event() {
+    // cached only when complete (or never recorded): the next owner's
+    // sync()/query() must not observe this owner's work
+    Caches& c = caches();
+    bool idle = c.on && hipEventQuery(e_) == hipSuccess;
+    c.events.release(device_, flags_, 1, e_, idle);
+  }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
   void record(uintptr_t stream) {
     HIP_CHECK(hipEventRecord(e_, (hipStream_t)stream));
   }
@@ -213,7 +387,20 @@ class Event {
 
  private:
   hipEvent_t e_ = nullptr;
+  uint64_t flags_;
+  int device_ = 0;
 };
+
+static py::dict stats_dict(const demodel::CacheStats& s) {
+  py::dict d;
+  d["hits"] = s.hits;
+  d["misses"] = s.misses;
+  d["bytes_cached"] = s.bytes_cached;
+  d["bytes_live"] = s.bytes_live;
+  d["freed"] = s.freed;
+  d["cap_bytes"] = s.cap_bytes;
+  return d;
+}
 
 // ------------------------------------------------------------------------
 // socket -> pinned drains (no GIL, MSG_WAITALL = one syscall per slab)
@@ -283,7 +470,19 @@ PYBIND11_MODULE(_hip, m) {
       .def_property_readonly("n_slabs", &PinnedPool::n_slabs)
       .def_property_readonly("slab_bytes", &PinnedPool::slab_bytes)
       .def("slab_ptr", &PinnedPool::slab_ptr)
-      .def("slab_view", &PinnedPool::slab_view);
+      .def("slab_view", &PinnedPool::slab_view)
+      .def("acquire", &PinnedPool::acquire, py::arg("slot"),
+           py::call_guard<py::gil_scoped_release>(),
+           "wait (no GIL) until the GPU has read the slot's last copy")
+      .def("submit", &PinnedPool::submit, py::arg("slot"), py::arg("dst"),
+           py::arg("nbytes"), py::arg("stream"),
+           py::call_guard<py::gil_scoped_release>(),
+           "H2D copy of the slot's first nbytes to dst + fence record")
+      .def("stream_wait", &PinnedPool::stream_wait, py::arg("slot"),
+           py::arg("stream"))
+      .def("drain", &PinnedPool::drain,
+           py::call_guard<py::gil_scoped_release>(),
+           "wait for every busy slot");
 
   py::class_<Stream>(m, "Stream")
       .def(py::init<int>(), py::arg("priority") = 0)
@@ -292,12 +491,29 @@ PYBIND11_MODULE(_hip, m) {
       .def_property_readonly("handle", &Stream::handle);
 
   py::class_<Event>(m, "Event")
-      .def(py::init<>())
+      .def(py::init<bool>(), py::arg("timing") = true)
       .def("record", &Event::record)
       .def("wait", &Event::wait)
       .def("sync", &Event::sync, py::call_guard<py::gil_scoped_release>())
       .def("query", &Event::query)
       .def("elapsed_ms", &Event::elapsed_ms);
+
+  m.def("cache_stats", [] {
+    Caches& c = caches();
+    py::dict d;
+    d["pinned"] = stats_dict(c.pinned.stats());
+    d["streams"] = stats_dict(c.streams.stats());
+    d["events"] = stats_dict(c.events.stats());
+    return d;
+  }, "hits/misses/bytes_cached/bytes_live/freed/cap_bytes of the pinned-"
+     "slab, stream and event caches (streams and events count 1 each)");
+  m.def("cache_trim", [] {
+    Caches& c = caches();
+    c.streams.trim();
+    c.events.trim();
+    return c.pinned.trim();
+  }, py::call_guard<py::gil_scoped_release>(),
+     "free everything idle in the caches; returns pinned bytes let go");
 
   m.def("h2d_async",
         [](uintptr_t dst, uintptr_t src, size_t n, uintptr_t stream) {

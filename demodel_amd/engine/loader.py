@@ -10,13 +10,13 @@ f32->bf16 cast path when the checkpoint dtype is wider than the model's.
 
 from __future__ import annotations
 
-import ctypes
 import struct
 
 from ..gpu import hip
 from .formats.safetensors import SafetensorsHeader
 
 _PIECE = 1 << 20  # scatter descriptor granularity (see load_into)
+_DESC_CLASS = 64 << 10  # descriptor buffers round up to this for reuse
 
 
 def load_into(blob, header: SafetensorsHeader, targets: dict,
@@ -98,10 +98,21 @@ def load_into(blob, header: SafetensorsHeader, targets: dict,
             raise KeyError(f"model is missing tensors: {sorted(missing)[:5]}"
                            f"{'...' if len(missing) > 5 else ''}")
 
+    dbuf = pin = None
+    pool = getattr(blob, "pool", None)
+    dcap = -(-len(desc) // _DESC_CLASS) * _DESC_CLASS
     if desc:
-        dbuf = h.DeviceBuffer(len(desc))
-        carr = (ctypes.c_char * len(desc)).from_buffer(desc)
-        h.h2d_async(dbuf.ptr, ctypes.addressof(carr), len(desc), handle)
+        # descriptor block: device side recycled through the landing
+        # BufferPool (no hipMalloc/hipFree per file per pull), host side
+        # staged in a cached pinned slab (a pageable source makes the
+        # "async" copy block on the stream's earlier work)
+        dbuf = pool.take(dcap) if pool is not None else None
+        if dbuf is None:
+            dbuf = h.DeviceBuffer(dcap)
+        pin = h.PinnedPool(dcap, 1)
+        pin.acquire(0)
+        pin.slab_view(0)[:len(desc)] = desc
+        pin.submit(0, dbuf.ptr, len(desc), handle)
         h.scatter_ranges(blob.buffer.ptr, dbuf.ptr, len(desc) // 32,
                          handle)
     for src_off, dst_ptr, n in casts:
@@ -109,6 +120,8 @@ def load_into(blob, header: SafetensorsHeader, targets: dict,
     # synchronous by contract: desc buffer and host staging must outlive
     # the launches
     s.sync()
+    if dbuf is not None and pool is not None:
+        pool.put(dbuf, dcap)
     return loaded
 
 

@@ -41,6 +41,8 @@ class LandedBlob:
     head: bytes = b""                 # first bytes (for header parsing)
     timings: dict = field(default_factory=dict)
     shared: bool = False              # registry-owned: recycle must skip
+    # the landing BufferPool: consumers recycle scratch buffers through it
+    pool: object = field(default=None, repr=False, compare=False)
 
     @property
     def chunk_digests(self) -> list[str]:
@@ -134,12 +136,14 @@ class Lander:
         self.slab_bytes = slab_bytes
         self.verify_chunk = verify_chunk
         self.head_bytes = head_bytes
+        # ring slabs, their fence events and both streams come from the
+        # native caches and go back to them when this lander dies (the
+        # ring drains first), so a lander per short-lived worker thread
+        # costs no hipHostMalloc after the first pull
         self.pool = self._h.PinnedPool(slab_bytes, n_slabs)
         self.buffer_pool = buffer_pool
         self.copy_stream = self._h.Stream(0)
         self.verify_stream = self._h.Stream(0)
-        self._slab_events = [self._h.Event() for _ in range(n_slabs)]
-        self._slab_busy = [False] * n_slabs
 
     def land(self, fill, nbytes: int, verify: bool = True,
              host_chain: bool = False, gpu_chain: bool = False,
@@ -167,7 +171,8 @@ class Lander:
         vc = verify_chunk or self.verify_chunk
         blob = LandedBlob(nbytes=nbytes,
                           device=f"cuda:{self.device_index}", buffer=buf,
-                          verify_chunk=vc, head=bytes(head))
+                          verify_chunk=vc, head=bytes(head),
+                          pool=self.buffer_pool)
         t_fill_done = time.perf_counter()
 
         if (verify or expected_digests is not None) and nbytes > 0:
@@ -238,8 +243,7 @@ class Lander:
         try:
             while off < nbytes:
                 slab = i % n_slabs
-                if self._slab_busy[slab]:
-                    self._slab_events[slab].sync()
+                self.pool.acquire(slab)
                 if hash_done is not None:
                     hash_done[slab].wait()
                 want = min(self.slab_bytes, nbytes - off)
@@ -261,15 +265,12 @@ class Lander:
                 if chain is not None:
                     hash_done[slab].clear()
                     hq.put((slab, view))
-                h.h2d_async(buf.ptr + base_off + off,
-                            self.pool.slab_ptr(slab),
-                            want, self.copy_stream.handle)
-                self._slab_events[slab].record(self.copy_stream.handle)
-                self._slab_busy[slab] = True
+                self.pool.submit(slab, buf.ptr + base_off + off, want,
+                                 self.copy_stream.handle)
                 if gpu_state is not None:
                     # chain over the landed region (whole 64B blocks only;
                     # the ragged tail is folded in at finalize)
-                    self._slab_events[slab].wait(self.verify_stream.handle)
+                    self.pool.stream_wait(slab, self.verify_stream.handle)
                     abs_off = base_off + off
                     nblk = (want if abs_off + want < file_size
                             else file_size - (file_size % 64) - abs_off
@@ -352,14 +353,14 @@ class Lander:
         hi_c = (file_size + vc - 1) // vc if hi >= file_size else hi // vc
         if hi_c <= lo_c:
             return None
-        done = h.Event()
+        done = h.Event(timing=False)
         done.record(self.copy_stream.handle)
         done.wait(self.verify_stream.handle)
         span = min(file_size, hi_c * vc) - lo_c * vc
         h.sha256_batch(buf.ptr + lo_c * vc, span, vc,
                        dig_dev.ptr + lo_c * 32, hi_c - lo_c,
                        self.verify_stream.handle)
-        ev = h.Event()
+        ev = h.Event(timing=False)
         ev.record(self.verify_stream.handle)
         return ev, lo_c, hi_c
 
@@ -368,9 +369,11 @@ class Lander:
         h = self._h
         vc = verify_chunk or self.verify_chunk
         n_chunks = (nbytes + vc - 1) // vc
-        dig_dev = h.DeviceBuffer(n_chunks * 32)
+        # recycled through the buffer pool: a hipFree per file per pull
+        # would synchronise the device under the files still landing
+        dig_dev = self.alloc(n_chunks * 32)
         # hash must see completed copies
-        done = h.Event()
+        done = h.Event(timing=False)
         done.record(self.copy_stream.handle)
         done.wait(self.verify_stream.handle)
         h.sha256_batch(buf.ptr, nbytes, vc, dig_dev.ptr,
@@ -383,6 +386,8 @@ class Lander:
         h.d2h_async(addr, dig_dev.ptr, n_chunks * 32,
                     self.verify_stream.handle)
         self.verify_stream.sync()
+        if self.buffer_pool is not None:
+            self.buffer_pool.put(dig_dev, max(n_chunks * 32, 1))
         # kernel writes big-endian words as native u32 -> swap to the
         # canonical sha256 byte order
         import numpy as np

@@ -94,9 +94,10 @@ class LanderPool:
     def __init__(self, device_index: int = 0, **kw):
         self._device_index = device_index
         self._kw = kw
+        # the thread-local slot is the only owner: a lander dies with its
+        # worker thread and its ring, streams and events go back to the
+        # native caches for the next pull's threads
         self._local = threading.local()
-        self._all: list = []
-        self._lock = threading.Lock()
         from .pipeline import BufferPool
 
         self.buffer_pool = BufferPool()
@@ -107,8 +108,6 @@ class LanderPool:
             lander = make_lander(self._device_index,
                                  buffer_pool=self.buffer_pool, **self._kw)
             self._local.lander = lander
-            with self._lock:
-                self._all.append(lander)
         return lander
 
     def recycle(self, result) -> int:
@@ -226,7 +225,8 @@ def _land_with_resume(lander, open_fn, nbytes: int, verify: bool,
     device = ("cpu" if isinstance(buf, bytearray)
               else f"cuda:{lander.device_index}")
     blob = LandedBlob(nbytes=nbytes, device=device, buffer=buf,
-                      verify_chunk=vc, head=bytes(head))
+                      verify_chunk=vc, head=bytes(head),
+                      pool=getattr(lander, "buffer_pool", None))
     if verify or expected_digests is not None:
         blob.digest_blob = lander.finish_verify(buf, nbytes, vc)
         if expected_digests is not None:
@@ -482,7 +482,8 @@ def _pull_segmented(landers: LanderPool, url: str, total: int, src0,
     if len(head) < min(total, lander0.head_bytes):
         head = lander0.read_head(buf, total)
     blob = LandedBlob(nbytes=total, device=f"cuda:{lander0.device_index}",
-                      buffer=buf, verify_chunk=vc, head=bytes(head))
+                      buffer=buf, verify_chunk=vc, head=bytes(head),
+                      pool=lander0.buffer_pool)
     blob._ranged = True  # on_range already fired per segment
     if not inc_verify:  # A/B fallback: whole-buffer tail hash
         blob.digest_blob = lander0._gpu_chunk_digests(buf, total, vc)
