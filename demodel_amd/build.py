@@ -3,7 +3,8 @@
 Two extensions, built straight with the toolchain (no setuptools overhead),
 .so files landing inside the package so they travel with a repo snapshot:
 
-* ``demodel_amd/_native.so``  — CPU helpers (libcrypto cert minting).
+* ``demodel_amd/_native.so``  — CPU helpers (libcrypto cert minting,
+  host zstd, the GIL-free socket loops of csrc/sock_io.h).
   Plain C++, no torch, builds and runs anywhere.
 * ``demodel_amd/_hip.so``     — the GPU pipeline: pinned-ring allocator,
   HIP streams/events, and the CDNA4 kernels (SHA-256, inflate, scatter,
@@ -46,11 +47,16 @@ def _run(cmd: list[str]) -> None:
     subprocess.run(cmd, check=True)
 
 
+# in-tree headers of _native.so (rebuild triggers)
+NATIVE_HDRS = [os.path.join(CSRC, "sock_io.h")]
+
+
 def build_native(force: bool = False) -> str:
     out = os.path.join(PKG_DIR, "_native.so")
     srcs = [os.path.join(CSRC, "certs.cpp"),
-            os.path.join(CSRC, "zstd_host.cpp")]
-    if not force and _newer(out, srcs):
+            os.path.join(CSRC, "zstd_host.cpp"),
+            os.path.join(CSRC, "sock_native.cpp")]
+    if not force and _newer(out, srcs + NATIVE_HDRS):
         return out
     cmd = (
         ["c++", "-O2", "-std=c++17", "-shared", "-fPIC",
@@ -77,7 +83,8 @@ HIP_SRCS = [
 
 # in-tree headers a source includes (rebuild triggers)
 HIP_HDRS = {
-    "hip_core.cpp": [os.path.join(CSRC, "resource_cache.h")],
+    "hip_core.cpp": [os.path.join(CSRC, "resource_cache.h"),
+                     os.path.join(CSRC, "sock_io.h")],
 }
 
 

@@ -3,7 +3,8 @@
 // Native equivalent of the data plane the reference left inside goproxy's
 // io.Copy loop (reference cmd/demodel/start.go:201-204; SURVEY.md §3.2 "HOT
 // LOOP"), rebuilt for MI355X: pinned host ring slabs, hipMemcpyAsync on side
-// streams, HIP events, socket->pinned drains that bypass Python, and DLPack
+// streams, HIP events, a socket->ring->HBM landing loop that bypasses Python
+// (PinnedPool::land_fd over csrc/sock_io.h), and DLPack
 // export so landed HBM blobs become zero-copy torch tensors.
 //
 // Deliberately torch-header-free: every API takes raw pointers/handles, so
@@ -17,7 +18,9 @@
 #include <sys/socket.h>
 #include <sys/types.h>
 #include <unistd.h>
+#include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -26,6 +29,7 @@
 #include <vector>
 
 #include "resource_cache.h"
+#include "sock_io.h"
 
 namespace py = pybind11;
 
@@ -166,6 +170,11 @@ class DeviceBuffer {
 // default geometry with workers=8 needs 16 rings x 4 x 32 MiB = 2 GiB, the
 // rest is room for the proxy's prefetch landers).  0 turns all three caches
 // off: every release frees, exactly as before the caches existed.
+//
+// DEMODEL_NATIVE_SOCK (read in Python, utils/netio.py) decides whether the
+// landers call PinnedPool::land_fd below or run their Python slab loop:
+// unset/1 = native receive and send loops, recv / send = that side only,
+// 0 = the Python loops on both ends.
 
 static const uint64_t kSlabGranule = 2ull << 20;
 static const uint64_t kHandleCap = 4096;  // idle streams / events, each
@@ -234,6 +243,8 @@ static Caches& caches() {
 // drains the ring's own fences, and synchronises the device when a raw
 // slab pointer was handed out (copies the ring did not see).  If any of
 // that fails the slabs are freed, not cached.
+static std::atomic<uint64_t> g_land_fd_calls{0};
+
 class PinnedPool {
  public:
   PinnedPool(size_t slab_bytes, int n_slabs) : slab_bytes_(slab_bytes) {
@@ -299,6 +310,85 @@ class PinnedPool {
   }
   void drain() {
     for (int i = 0; i < (int)busy_.size(); i++) acquire(i);
+  }
+
+  struct LandResult {
+    uint64_t landed = 0;  // bytes whose H2D copy was submitted
+    int status = 0;       // sock_io.h status of the receive that ended it
+    double recv_s = 0;
+    uint64_t recv_calls = 0;
+  };
+  // The landing loop for one byte range of a plain-TCP body, run without
+  // the GIL: acquire slot, receive a slab's worth, copy into the head
+  // buffer while it has room, submit, next slot.  Measured on the flagship
+  // (profiles/native_socket_loops_ab.md): the blocking fd takes a 32 MiB
+  // slab in 1.00 recv(MSG_WAITALL) calls where the timeout-mode Python
+  // socket needed 17.1 poll+recv pairs.
+  //
+  // The first `prefilled` bytes of slot `slot0` are already in place (body
+  // bytes that arrived with the response head; the caller acquired the
+  // slot).  A receive that ends short stops the loop: whole slabs landed so
+  // far are counted, the broken slab is not submitted.
+  LandResult land_fd(int fd, uintptr_t dst, size_t nbytes, uintptr_t stream,
+                     uintptr_t head_ptr, size_t head_cap,
+                     int stall_timeout_ms, int slot0, size_t prefilled) {
+    LandResult res;
+    const int n = (int)slabs_.size();
+    if (n == 0) throw std::invalid_argument("land_fd: ring has no slabs");
+    if (slot0 < 0 || slot0 >= n)
+      throw std::out_of_range("land_fd: slot0 outside the ring");
+    if (prefilled > slab_bytes_ || prefilled > nbytes)
+      throw std::out_of_range("land_fd: prefilled exceeds the first slab");
+    g_land_fd_calls++;
+    demodel::RecvSession sess(fd, stall_timeout_ms);
+    size_t off = 0, head_len = 0;
+    int slot = slot0;
+    while (off < nbytes) {
+      size_t want = nbytes - off < slab_bytes_ ? nbytes - off : slab_bytes_;
+      size_t got = 0;
+      if (off == 0 && prefilled) {
+        got = prefilled;
+      } else {
+        acquire(slot);
+      }
+      char* slab = (char*)slabs_[slot];
+      if (got < want) {
+        auto t0 = std::chrono::steady_clock::now();
+        demodel::IoResult r =
+            sess.recv(slab + got, want - got, &res.recv_calls);
+        res.recv_s += std::chrono::duration<double>(
+                          std::chrono::steady_clock::now() - t0).count();
+        if (r.bytes < want - got) {
+          res.status = r.status ? r.status : demodel::kSockEof;
+          break;
+        }
+      }
+      if (head_ptr && head_len < head_cap) {
+        size_t take = want < head_cap - head_len ? want : head_cap - head_len;
+        memcpy((char*)head_ptr + head_len, slab, take);
+        head_len += take;
+      }
+      submit(slot, dst + off, want, stream);
+      off += want;
+      res.landed = off;
+      slot = (slot + 1) % n;
+    }
+    return res;
+  }
+
+  // Expand (src_off, dst_ptr, nbytes) u64 triples into scatter RangeDesc
+  // records of at most `piece` bytes, straight into slab `slot`.  Throws
+  // when they do not fit; never writes a partial table.
+  uint64_t write_scatter_descs(int slot, const uint64_t* triples,
+                               size_t n_triples, uint64_t piece) {
+    void* slab = slabs_.at(slot);
+    int64_t n = demodel::expand_scatter_descs(
+        triples, n_triples, piece, (uint64_t*)slab,
+        slab_bytes_ / (demodel::kRangeDescWords * sizeof(uint64_t)));
+    if (n < 0)
+      throw std::out_of_range(
+          "write_scatter_descs: descriptors exceed the slab");
+    return (uint64_t)n;
   }
 
  private:
@@ -403,22 +493,7 @@ static py::dict stats_dict(const demodel::CacheStats& s) {
 }
 
 // ------------------------------------------------------------------------
-// socket -> pinned drains (no GIL, MSG_WAITALL = one syscall per slab)
-
-static ssize_t drain_fd(int fd, uintptr_t dst, size_t want) {
-  char* p = (char*)dst;
-  size_t got = 0;
-  while (got < want) {
-    ssize_t n = recv(fd, p + got, want - got, MSG_WAITALL);
-    if (n < 0) {
-      if (errno == EINTR) continue;
-      return -errno;
-    }
-    if (n == 0) break;  // EOF
-    got += (size_t)n;
-  }
-  return (ssize_t)got;
-}
+// file -> pinned reads (no GIL)
 
 static ssize_t read_file_into(int fd, uintptr_t dst, size_t want,
                               int64_t offset) {
@@ -482,7 +557,43 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("stream"))
       .def("drain", &PinnedPool::drain,
            py::call_guard<py::gil_scoped_release>(),
-           "wait for every busy slot");
+           "wait for every busy slot")
+      .def("land_fd",
+           [](PinnedPool& self, int fd, uintptr_t dst, size_t nbytes,
+              uintptr_t stream, uintptr_t head_ptr, size_t head_cap,
+              int stall_timeout_ms, int slot0, size_t prefilled) {
+             PinnedPool::LandResult r;
+             {
+               py::gil_scoped_release nogil;
+               r = self.land_fd(fd, dst, nbytes, stream, head_ptr, head_cap,
+                                stall_timeout_ms, slot0, prefilled);
+             }
+             return py::make_tuple(r.landed, r.status, r.recv_s,
+                                   r.recv_calls);
+           },
+           py::arg("fd"), py::arg("dst"), py::arg("nbytes"),
+           py::arg("stream"), py::arg("head_ptr"), py::arg("head_cap"),
+           py::arg("stall_timeout_ms"), py::arg("slot0") = 0,
+           py::arg("prefilled") = 0,
+           "land nbytes of a plain-TCP body fd -> ring -> dst without the "
+           "GIL -> (bytes landed, status, recv seconds, recv calls); status "
+           "0 ok, -1 EOF, ETIMEDOUT stall, else errno.  The first min(nbytes"
+           ", head_cap) bytes are also copied to head_ptr (0 = no head)")
+      .def("write_scatter_descs",
+           [](PinnedPool& self, int slot, py::buffer triples,
+              uint64_t piece) {
+             py::buffer_info info = triples.request();
+             size_t nb = (size_t)info.size * (size_t)info.itemsize;
+             if (nb % 24 || ((uintptr_t)info.ptr & 7))
+               throw std::invalid_argument(
+                   "write_scatter_descs: triples must be aligned u64 x 3");
+             return self.write_scatter_descs(
+                 slot, (const uint64_t*)info.ptr, nb / 24, piece);
+           },
+           py::arg("slot"), py::arg("triples"), py::arg("piece"),
+           "expand (src_off, dst_ptr, nbytes) u64 triples into 32-byte "
+           "scatter descriptors of <= piece bytes in the slab; returns the "
+           "descriptor count, raises if they exceed the slab");
 
   py::class_<Stream>(m, "Stream")
       .def(py::init<int>(), py::arg("priority") = 0)
@@ -537,10 +648,14 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::call_guard<py::gil_scoped_release>());
 
-  m.def("drain_fd", &drain_fd, py::arg("fd"), py::arg("dst"),
-        py::arg("want"), py::call_guard<py::gil_scoped_release>(),
-        "recv() a TCP fd into a pinned slab without the GIL; returns bytes "
-        "read (0..want; <0 = -errno)");
+  m.def("sock_stats", [] {
+    demodel::SockCounters& c = demodel::sock_counters();
+    py::dict d;
+    d["recv_exact"] = c.recv_exact.load();
+    d["recv_calls"] = c.recv_calls.load();
+    d["land_fd"] = g_land_fd_calls.load();
+    return d;
+  }, "native landing-loop counters of this extension since import");
   m.def("read_file_into", &read_file_into, py::arg("fd"), py::arg("dst"),
         py::arg("want"), py::arg("offset") = -1,
         py::call_guard<py::gil_scoped_release>());

@@ -1,9 +1,15 @@
 """Synchronous HTTP blob fetcher for the pull engine.
 
 One GET per blob, body drained straight into the caller's buffers
-(pinned ring slabs on GPU machines) with MSG_WAITALL — one syscall per
-slab on plain TCP.  TLS uses the same interface via recv_into on the
-wrapped socket.  Redirects are followed here (the HF hub -> CDN hop).
+(pinned ring slabs on GPU machines).  A plain-TCP, Content-Length framed
+body is handed to the landers as a bare fd (native_body) and received by
+the native loop of csrc/sock_io.h: blocking recv(MSG_WAITALL), measured
+1.00 recv per 32 MiB slab.  fill() is the Python path for everything else
+(TLS, chunked, EOF-delimited) and the DEMODEL_NATIVE_SOCK=0 fallback; its
+sockets are in timeout mode, so the fd is O_NONBLOCK, MSG_WAITALL returns
+whatever is queued, and a slab took 17.1 poll+recv pairs on the same box
+(profiles/native_socket_loops_ab.md).  Redirects are followed here (the
+HF hub -> CDN hop).
 
 This replaces the client->goproxy->origin relay of the reference with an
 engine-native client path; the proxy (proxy/server.py) remains the
@@ -20,8 +26,14 @@ import zlib
 from dataclasses import dataclass, field
 from urllib.parse import urlsplit
 
+from ..utils.netio import native_sock
+
 MAX_REDIRECTS = 5
 HEAD_LIMIT = 256 * 1024
+
+# recv_into calls made by BlobSource.fill on closed sources, for A/B tables
+# (racy adds from worker threads: a statistic, not an invariant)
+PY_RECV_CALLS = 0
 
 
 class FetchError(Exception):
@@ -66,6 +78,41 @@ class BlobSource:
         self._remaining = self.length
         self._chunk_rem = 0
         self._eof = False
+        self.recv_calls = 0
+        t = sock.gettimeout() if hasattr(sock, "gettimeout") else None
+        self.stall_ms = int((t or 60.0) * 1000)
+
+    # ---- native hand-over ---------------------------------------------
+
+    @property
+    def native_eligible(self) -> bool:
+        """Plain TCP with Content-Length framing: the landers may take
+        the body off the fd themselves (once leftover_pending() is
+        False)."""
+        return (not self._tls and not self._chunked and self.length >= 0
+                and native_sock("recv"))
+
+    def leftover_pending(self) -> bool:
+        """Body bytes that arrived with the response head and are still
+        to be delivered through fill()."""
+        return self._left is not None and len(self._left) > 0
+
+    def native_body(self):
+        """(fd, remaining body bytes) for a native receive loop, or
+        None: TLS, chunked and EOF-delimited bodies, pending leftover
+        bytes and closed sockets stay on fill().  Report what the loop
+        took with native_consumed()."""
+        if not self.native_eligible or self.leftover_pending():
+            return None
+        fd = self.sock.fileno()
+        if fd < 0:
+            return None
+        return fd, max(self._remaining, 0)
+
+    def native_consumed(self, n: int) -> None:
+        self._remaining -= n
+        if self._remaining <= 0:
+            self._eof = True
 
     # ---- raw reads ----------------------------------------------------
 
@@ -115,6 +162,7 @@ class BlobSource:
                 return 0
             want = min(len(view), self._remaining)
             if not self._tls and (self._left is None or not len(self._left)):
+                self.recv_calls += 1
                 got = self.sock.recv_into(view[:want], want,
                                           socket.MSG_WAITALL)
             else:
@@ -174,6 +222,9 @@ class BlobSource:
         return body
 
     def close(self):
+        global PY_RECV_CALLS
+        PY_RECV_CALLS += self.recv_calls
+        self.recv_calls = 0
         try:
             self.sock.close()
         except OSError:

@@ -78,6 +78,34 @@ class DigestMismatch(IOError):
             f"(byte offset {chunk_index * verify_chunk})")
 
 
+def _native_source(fill, chain, gpu_state):
+    """The BlobSource behind `fill` when its body may be received by a
+    native loop (csrc/sock_io.h), else None: host/GPU chains hash slab by
+    slab in Python, and TLS, chunked or owner-less callables have no bare
+    fd to hand over."""
+    if chain is not None or gpu_state is not None:
+        return None
+    src = getattr(fill, "__self__", None)
+    if src is None or getattr(fill, "__name__", "") != "fill":
+        return None
+    if not getattr(src, "native_eligible", False):
+        return None
+    return src
+
+
+def _native_failure(status: int) -> OSError | None:
+    """sock_io.h status -> the exception a Python recv would have raised
+    (None for a clean EOF, which fill() reports by returning 0)."""
+    import errno
+    import os
+
+    if status < 0:
+        return None
+    if status == errno.ETIMEDOUT:
+        return TimeoutError("timed out")
+    return OSError(status, os.strerror(status))
+
+
 def check_digests(got: bytes, expected: bytes, verify_chunk: int) -> None:
     if got == expected:
         return
@@ -207,6 +235,10 @@ class Lander:
 
         Returns (head_bytes, fill_seconds)."""
         h = self._h
+        src = _native_source(fill, chain, gpu_state)
+        if src is not None:
+            return self._land_native(buf, base_off, src, fill, nbytes,
+                                     keep_head)
         head = bytearray()
         n_slabs = self.pool.n_slabs
         file_size = file_size if file_size is not None else base_off + nbytes
@@ -287,6 +319,52 @@ class Lander:
                 hq.put(None)
                 hasher.join()
         return head, fill_s
+
+    def _land_native(self, buf, base_off: int, src, fill, nbytes: int,
+                     keep_head: bool) -> tuple[bytearray, float]:
+        """land_into for a plain-TCP Content-Length body: the whole
+        acquire/recv/head/submit loop runs in PinnedPool.land_fd with the
+        GIL released once.  Body bytes that came with the response head
+        go into the first slab through fill() first."""
+        import ctypes
+
+        if nbytes <= 0:
+            return bytearray(), 0.0
+        pool = self.pool
+        tf = time.perf_counter()
+        pre = 0
+        if src.leftover_pending():
+            pool.acquire(0)
+            view = pool.slab_view(0)[:min(self.slab_bytes, nbytes)]
+            while pre < len(view) and src.leftover_pending():
+                try:
+                    n = fill(view[pre:])
+                except Exception as e:
+                    raise LandingError(0, e) from e
+                if n <= 0:
+                    raise LandingError(0)
+                pre += n
+        fill_s = time.perf_counter() - tf
+        body = src.native_body()
+        if body is None:  # socket already closed
+            raise LandingError(0, OSError("source has no open socket"))
+        fd, remaining = body
+        total = min(nbytes, pre + remaining)
+        head = bytearray(min(self.head_bytes, total) if keep_head else 0)
+        head_ref = head_ptr = 0
+        if head:
+            head_ref = (ctypes.c_char * len(head)).from_buffer(head)
+            head_ptr = ctypes.addressof(head_ref)
+        try:
+            landed, status, recv_s, _calls = pool.land_fd(
+                fd, buf.ptr + base_off, total, self.copy_stream.handle,
+                head_ptr, len(head), src.stall_ms, 0, pre)
+        finally:
+            del head_ref  # a bytearray with a live export cannot resize
+        src.native_consumed(max(landed - pre, 0))
+        if status != 0 or landed < nbytes:
+            raise LandingError(landed, _native_failure(status))
+        return head, fill_s + recv_s
 
     def sync(self) -> None:
         self.copy_stream.sync()
@@ -487,11 +565,30 @@ class HostLander:
         mv = memoryview(buf)
         off = 0
         t0 = time.perf_counter()
+        src = _native_source(fill, chain, gpu_state)
+        recv_exact = None
+        if src is not None:
+            from .. import _native
+
+            recv_exact = _native.recv_exact
         while off < nbytes:
             want = min(self.slab_bytes, nbytes - off)
             got = 0
             while got < want:
                 lo = base_off + off + got
+                body = None if recv_exact is None else src.native_body()
+                if body is not None:
+                    # straight into the bytearray, GIL released once per
+                    # slab; leftover head bytes went through fill() below
+                    fd, remaining = body
+                    n, status, _calls = recv_exact(
+                        fd, mv, lo, min(want - got, remaining),
+                        src.stall_ms)
+                    src.native_consumed(n)
+                    got += n
+                    if got < want:
+                        raise LandingError(off, _native_failure(status))
+                    continue
                 try:
                     n = fill(mv[lo:base_off + off + want])
                 except Exception as e:

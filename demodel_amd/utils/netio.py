@@ -1,11 +1,14 @@
 """Async-friendly high-throughput socket IO helpers.
 
-sendfile_threaded: a blocking os.sendfile loop on a worker thread, used
+sendfile_threaded: a blocking sendfile loop on a worker thread, used
 for blob bodies by both the proxy's cache-hit serving and the test/bench
 origin.  asyncio's loop.sendfile serializes all streams through the event
 loop thread and tops out ~3x lower at 4+ parallel blob streams
 (scripts/net_probe.py); a thread per in-flight body keeps every byte in
-kernel space and scales with cores.
+kernel space and scales with cores.  The loop itself is native
+(csrc/sock_io.h sendfile_exact: GIL released once, fd blocking for the
+call, about one syscall per 2 GiB); DEMODEL_NATIVE_SOCK selects the old
+Python loops per side.
 """
 
 from __future__ import annotations
@@ -16,6 +19,28 @@ import os
 import select as sel
 
 _POOL: cf.ThreadPoolExecutor | None = None
+
+# a body whose peer accepts no byte for this long is given up (the Python
+# loop re-armed its 10 s select for ever)
+SEND_STALL_MS = 60_000
+
+# os.sendfile calls made by the Python loop, for A/B tables (racy adds from
+# pool threads: a statistic, not an invariant)
+PY_SENDFILE_CALLS = 0
+
+
+def native_sock(side: str) -> bool:
+    """Whether `side` ("recv" or "send") runs its socket loop natively.
+
+    DEMODEL_NATIVE_SOCK: unset/"1" both sides, "0" neither (the Python
+    loops, as before the native ones existed), "recv" / "send" that side
+    only.  Read per call so tests and A/B runs can flip it."""
+    v = os.environ.get("DEMODEL_NATIVE_SOCK", "1").strip().lower()
+    if v in ("", "1", "on", "both"):
+        return True
+    if v in ("0", "off"):
+        return False
+    return v == side
 
 
 def _pool() -> cf.ThreadPoolExecutor:
@@ -248,10 +273,36 @@ async def sendfile_threaded(writer: asyncio.StreamWriter, f,
     fd = sock.fileno()
     infd = f.fileno()
 
+    def run_native():
+        import errno
+
+        from .. import _native
+
+        # a duplicate, so that restoring O_NONBLOCK after the call can never
+        # hit an fd number the loop closed and reused meanwhile (the flag
+        # lives on the shared open file description)
+        own = os.dup(fd)
+        try:
+            sent, status, _calls = _native.sendfile_exact(
+                own, infd, start, length, SEND_STALL_MS)
+        finally:
+            os.close(own)
+        if status == 0:
+            return
+        if status < 0:
+            raise ConnectionResetError(
+                f"file ended after {sent} of {length} bytes")
+        if status == errno.ETIMEDOUT:
+            raise TimeoutError(
+                f"peer stalled after {sent} of {length} bytes")
+        raise OSError(status, os.strerror(status))
+
     def run():
+        global PY_SENDFILE_CALLS
         off = start
         remaining = length
         while remaining > 0:
+            PY_SENDFILE_CALLS += 1
             try:
                 sent = os.sendfile(fd, infd, off, remaining)
             except BlockingIOError:
@@ -264,7 +315,8 @@ async def sendfile_threaded(writer: asyncio.StreamWriter, f,
 
     loop = asyncio.get_running_loop()
     try:
-        await loop.run_in_executor(_pool(), run)
+        await loop.run_in_executor(
+            _pool(), run_native if native_sock("send") else run)
     finally:
         try:
             writer.transport.resume_reading()
