@@ -8,8 +8,8 @@ Two extensions, built straight with the toolchain (no setuptools overhead),
   Plain C++, no torch, builds and runs anywhere.
 * ``demodel_amd/_hip.so``     — the GPU pipeline: pinned-ring allocator,
   HIP streams/events, and the CDNA4 kernels (SHA-256, inflate, scatter,
-  GGUF dequant).  Compiled with hipcc for gfx950 only; importable on a
-  CPU-only box (calls fail until a GPU is present).
+  GGUF and FP8 dequant).  Compiled with hipcc for gfx950 only; importable
+  on a CPU-only box (calls fail until a GPU is present).
 """
 
 from __future__ import annotations
@@ -73,6 +73,7 @@ HIP_SRCS = [
     "hip_core.cpp",
     "sha256.hip",
     "scatter.hip",
+    "fp8_dequant.hip",
     "gguf_dequant.hip",
     "inflate.hip",
     "zstd_kernel.hip",

@@ -21,6 +21,7 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -56,6 +57,11 @@ void launch_scatter_ranges(const void* src, const uint64_t* desc,
                            int n_desc, hipStream_t stream);
 void launch_cast_f32_to_bf16(const float* src, uint16_t* dst, size_t n,
                              hipStream_t stream);
+void launch_fp8_block_dequant(const void* src_fp8, const void* scale,
+                              int scale_dtype, void* dst, int dst_dtype,
+                              int64_t rows, int64_t cols, int64_t block_rows,
+                              int64_t block_cols, hipStream_t stream);
+void fp8_block_dequant_pass_limits(int64_t* out);
 void launch_gguf_dequant(int qtype, const void* src, uint16_t* dst_bf16,
                          int64_t n_blocks, hipStream_t stream);
 void launch_inflate_streams(const uint64_t* desc, int n_streams,
@@ -699,6 +705,43 @@ PYBIND11_MODULE(_hip, m) {
                                   (hipStream_t)stream);
         },
         py::call_guard<py::gil_scoped_release>());
+  m.def("fp8_block_dequant",
+        [](uintptr_t src, uintptr_t scale, int scale_dtype, uintptr_t dst,
+           int dst_dtype, int64_t rows, int64_t cols, int64_t block_rows,
+           int64_t block_cols, uintptr_t stream) {
+          if (scale_dtype < 0 || scale_dtype > 2)
+            throw std::invalid_argument(
+                "fp8_block_dequant: scale_dtype must be 0=f32 1=bf16 2=f16");
+          if (dst_dtype < 0 || dst_dtype > 1)
+            throw std::invalid_argument(
+                "fp8_block_dequant: dst_dtype must be 0=bf16 1=f32");
+          if (rows < 0 || cols < 0)
+            throw std::invalid_argument(
+                "fp8_block_dequant: negative shape");
+          if (block_rows <= 0 || block_cols <= 0)
+            throw std::invalid_argument(
+                "fp8_block_dequant: block must be positive");
+          if (cols && rows > INT64_MAX / 4 / cols)
+            throw std::invalid_argument(
+                "fp8_block_dequant: shape overflows");
+          launch_fp8_block_dequant((const void*)src, (const void*)scale,
+                                   scale_dtype, (void*)dst, dst_dtype, rows,
+                                   cols, block_rows, block_cols,
+                                   (hipStream_t)stream);
+        },
+        py::arg("src"), py::arg("scale"), py::arg("scale_dtype"),
+        py::arg("dst"), py::arg("dst_dtype"), py::arg("rows"),
+        py::arg("cols"), py::arg("block_rows"), py::arg("block_cols"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>(),
+        "widen a row-major [rows, cols] OCP e4m3fn tensor to bf16/f32, "
+        "multiplying by scale[r / block_rows][c / block_cols]");
+  m.def("fp8_block_dequant_pass_limits", [] {
+          int64_t lim[2];
+          fp8_block_dequant_pass_limits(lim);
+          return py::make_tuple(lim[0], lim[1]);
+        },
+        "(elements, columns of one row) that one pass of "
+        "fp8_block_dequant's largest grid covers");
   m.def("gguf_dequant",
         [](int qtype, uintptr_t src, uintptr_t dst, int64_t n_blocks,
            uintptr_t stream) {

@@ -50,6 +50,88 @@ class SafetensorsHeader:
         return max((t.end for t in self.tensors), default=0)
 
 
+@dataclass
+class Fp8Scale:
+    """The scale tensor that goes with one F8_E4M3 weight: element
+    [r, c] of the weight multiplies scale[r // block[0], c // block[1]]."""
+    info: TensorInfo
+    block: tuple[int, int]     # (block_rows, block_cols)
+
+
+_FP8_SCALE_DTYPES = ("F32", "BF16", "F16")
+_FP8_DEFAULT_BLOCK = (128, 128)
+
+
+def _numel(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
+def _resolve_fp8_block(name, shape, sshape, block_size):
+    R, C = shape
+    if _numel(sshape) == 1 and len(sshape) <= 1:
+        return (max(R, 1), max(C, 1))                    # per tensor
+    if sshape in ((R,), (R, 1)):
+        return (1, max(C, 1))                            # per output row
+    if len(sshape) == 2:
+        sr, sc = sshape
+        for cand in (block_size, _FP8_DEFAULT_BLOCK):
+            if cand is None:
+                continue
+            br, bc = (int(x) for x in cand)
+            if br > 0 and bc > 0 and \
+                    (-(-R // br), -(-C // bc)) == (sr, sc):
+                return (br, bc)
+        if sr > 0 and sc > 0 and R and C and R % sr == 0 and C % sc == 0:
+            return (R // sr, C // sc)
+    raise ValueError(
+        f"{name}: scale shape {sshape} fits no block of weight shape "
+        f"{shape}")
+
+
+def fp8_scale_map(header: SafetensorsHeader,
+                  block_size=None) -> dict[str, Fp8Scale]:
+    """Find the scale tensor of every F8_E4M3 tensor X in the header:
+    X + "_scale_inv" (one scale per 128x128 block in published
+    checkpoints) or else X + "_scale" (compressed-tensors: per tensor or
+    per output row).  Both multiply.  `block_size` is the checkpoint's
+    quantization_config.weight_block_size when it has one.
+
+    Returns weight name -> Fp8Scale; FP8 tensors without a scale tensor
+    are absent.  Raises ValueError for a scale of the wrong dtype, a
+    scaled weight that is not 2-D, or a scale shape that fits no block.
+    """
+    if block_size is not None:
+        if len(block_size) != 2:
+            raise ValueError(f"block_size must be (rows, cols), got "
+                             f"{block_size!r}")
+        block_size = tuple(int(x) for x in block_size)
+    by_name = {t.name: t for t in header.tensors}
+    out = {}
+    for t in header.tensors:
+        if t.st_dtype != "F8_E4M3":
+            continue
+        sinfo = by_name.get(t.name + "_scale_inv") or \
+            by_name.get(t.name + "_scale")
+        if sinfo is None:
+            continue
+        if sinfo.st_dtype not in _FP8_SCALE_DTYPES:
+            raise ValueError(
+                f"{sinfo.name}: scale dtype {sinfo.st_dtype} is not one of "
+                f"{_FP8_SCALE_DTYPES}")
+        if len(t.shape) != 2:
+            raise ValueError(
+                f"{t.name}: FP8 tensor with a scale must be 2-D, got shape "
+                f"{t.shape}")
+        out[t.name] = Fp8Scale(
+            info=sinfo,
+            block=_resolve_fp8_block(t.name, t.shape, sinfo.shape,
+                                     block_size))
+    return out
+
+
 def parse_header(prefix: bytes) -> SafetensorsHeader:
     """Parse from the first bytes of a safetensors file.
 

@@ -202,6 +202,29 @@ def write_parquet_shards(out_dir: str, n_shards: int = 8,
     return files
 
 
+def quantize_fp8_blocks(w_f32, block: tuple[int, int]):
+    """Block-quantise a 2-D f32 torch tensor the way published FP8
+    checkpoints do: per (block_rows, block_cols) block, scale = amax / 448
+    (the largest e4m3fn value), floored at a small positive value so an
+    all-zero block divides cleanly; code = e4m3fn(w / scale).
+
+    Returns (uint8 codes [R, C], f32 scales [ceil(R/br), ceil(C/bc)]);
+    codes * scales, expanded over the blocks, approximates w."""
+    import torch
+
+    R, C = w_f32.shape
+    br, bc = block
+    sr, sc = -(-R // br), -(-C // bc)
+    pad = torch.zeros(sr * br, sc * bc, dtype=torch.float32)
+    pad[:R, :C] = w_f32.detach().float()
+    amax = pad.view(sr, br, sc, bc).abs().amax(dim=(1, 3))
+    scales = (amax / 448.0).clamp_min(1e-12)
+    full = scales.repeat_interleave(br, 0)[:R].repeat_interleave(bc, 1)[:, :C]
+    q = (w_f32.detach().float() / full).clamp(-448.0, 448.0)
+    codes = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), scales.contiguous()
+
+
 def gguf_tensor_specs(geom: dict, qtype: int = 12):
     """(name, ggml_dims, type_id) specs for a llama-shaped GGUF."""
     tensors = []
