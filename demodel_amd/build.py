@@ -8,7 +8,7 @@ Two extensions, built straight with the toolchain (no setuptools overhead),
   Plain C++, no torch, builds and runs anywhere.
 * ``demodel_amd/_hip.so``     — the GPU pipeline: pinned-ring allocator,
   HIP streams/events, and the CDNA4 kernels (SHA-256, inflate, scatter,
-  GGUF and FP8 dequant).  Compiled with hipcc for gfx950 only; importable
+  GGUF and FP8 dequant, parquet page decode).  Compiled with hipcc for gfx950 only; importable
   on a CPU-only box (calls fail until a GPU is present).
 """
 
@@ -79,6 +79,7 @@ HIP_SRCS = [
     "zstd_kernel.hip",
     "snappy.hip",
     "lz4.hip",
+    "parquet_decode.hip",
 ]
 
 

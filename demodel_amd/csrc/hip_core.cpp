@@ -72,6 +72,10 @@ void launch_snappy_streams(const uint64_t* desc, int n_streams,
                            hipStream_t stream);
 void launch_lz4_streams(const uint64_t* desc, int n_streams,
                         hipStream_t stream);
+void launch_parquet_decode(const uint64_t* desc, int n_pages,
+                           hipStream_t stream, int max_blocks);
+void launch_parquet_hybrid(const uint64_t* desc, int n_streams,
+                           hipStream_t stream, int max_blocks);
 }
 
 // ------------------------------------------------------------------------
@@ -786,4 +790,28 @@ PYBIND11_MODULE(_hip, m) {
         "LZ4 raw-block decompress n_streams descriptors (8 u64 each: "
         "src, src_len, dst, dst_cap, written, status, consumed, pad), "
         "wave per stream (parquet LZ4/LZ4_RAW page codecs)");
+  m.def("parquet_hybrid",
+        [](uintptr_t desc, int n_streams, uintptr_t stream,
+           int max_blocks) {
+          launch_parquet_hybrid((const uint64_t*)desc, n_streams,
+                                (hipStream_t)stream, max_blocks);
+        },
+        py::call_guard<py::gil_scoped_release>(), py::arg("desc"),
+        py::arg("n_streams"), py::arg("stream"),
+        py::arg("max_blocks") = 0,
+        "decode n_streams bare RLE/bit-packed hybrid streams (8 u64 "
+        "each: src, src_len, dst, count, bit_width, limit, status, "
+        "matched) into u32 values, wave per stream; max_blocks caps the "
+        "grid (0: default)");
+  m.def("parquet_decode",
+        [](uintptr_t desc, int n_pages, uintptr_t stream, int max_blocks) {
+          launch_parquet_decode((const uint64_t*)desc, n_pages,
+                                (hipStream_t)stream, max_blocks);
+        },
+        py::call_guard<py::gil_scoped_release>(), py::arg("desc"),
+        py::arg("n_pages"), py::arg("stream"), py::arg("max_blocks") = 0,
+        "decode n_pages decompressed parquet data pages (16 u64 each: "
+        "src, src_len, dict, dict_count, out_vals, out_def, out_rep, "
+        "scratch, num_values, params, rep_len, def_len, status, non_null, "
+        "consumed, pad) into entry-aligned typed buffers, wave per page");
 }

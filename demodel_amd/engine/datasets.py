@@ -34,16 +34,28 @@ class ShardBatch:
     name: str
     data: object            # torch.uint8 tensor (device or cpu)
     spans: list             # [(offset, length)] decompressed record spans
+    # parquet shards streamed with columns=...: formats.parquet.Columns
+    # (name -> Column of device tensors, plus .skipped)
+    columns: dict | None = None
 
     def tensors(self):
         return [self.data[o:o + n] for o, n in self.spans]
 
 
-def _prep_parquet_gpu(blob):
+def _prep_parquet_gpu(blob, columns=None):
+    """prep_pages_gpu's plan plus, when columns is not None, the
+    ColumnDecode that turns the decompressed pages into tensors."""
     from .formats import parquet as pqf
 
-    pages = pqf.blob_pages(blob)
-    return pqf.prep_pages_gpu(blob, pages)
+    if columns is None:
+        return pqf.prep_pages_gpu(blob, pqf.blob_pages(blob)) + (None,)
+    meta, chunk_pages = pqf.blob_meta_pages(blob)
+    plan = pqf.plan_columns(meta, chunk_pages, columns)
+    pages = [(cm.codec, info)
+             for cm, cp in zip(meta.chunks, chunk_pages) for info in cp]
+    prep = pqf.prep_pages_gpu(blob, pages)
+    ring, spans = prep[5], prep[6]
+    return prep + (pqf.ColumnDecode(plan, ring.ptr, spans.__getitem__),)
 
 
 def _prep_zst_frames_gpu(blob, idx):
@@ -93,8 +105,16 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                    landers: LanderPool | None = None,
                    digest_map: dict | None = None,
                    on_file=None, inflight: int = 4, eager: bool = True,
-                   repo_type: str = "model"):
+                   repo_type: str = "model",
+                   columns: tuple | None = None):
     """Yield ShardBatch per data shard of an HF dataset repo.
+
+    columns=None (default) yields the decompressed pages only.  A tuple
+    of column names, or () for every column the decoder supports, also
+    decodes parquet shards' pages into typed device tensors in the same
+    job that decompressed them (formats.parquet.decode_columns_gpu says
+    what is supported); they arrive as ShardBatch.columns.  .zst shards
+    are unaffected.
 
     inflight bounds how many decompressed shard rings can be in flight
     (launched but not yet yielded) at once — the HBM high-water mark is
@@ -139,6 +159,7 @@ def stream_dataset(repo: str, endpoint: str | None = None,
         all_deflate = []
         all_lz4 = []
         all_copies = []
+        decodes = []
         entries = []
         for f in shards:
             if f.name.endswith(".parquet"):
@@ -147,19 +168,22 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                         "parquet streaming needs a GPU (CPU fallback "
                         "covers .zst shards)")
                 (frames, snappy, deflate, lz4, copies, ring,
-                 spans) = _prep_parquet_gpu(f.blob)
+                 spans, decode) = _prep_parquet_gpu(f.blob, columns)
             else:
                 idx = _sidecar_idx(f.sidecar)
                 if not gpu:
                     data, spans = _decompress_cpu(f.blob, idx)
-                    out.append((f, None, data, spans))
+                    out.append((f, None, data, spans, None))
                     continue
                 (frames, snappy, deflate, lz4, copies, ring,
                  spans) = _prep_zst_frames_gpu(f.blob, idx)
+                decode = None
             entries.append((f, len(all_frames), len(frames),
                             len(all_snappy), len(snappy),
                             len(all_deflate), len(deflate),
-                            len(all_lz4), len(lz4), ring, spans))
+                            len(all_lz4), len(lz4), ring, spans, decode))
+            if decode is not None:
+                decodes.append(decode)
             all_frames += frames
             all_snappy += snappy
             all_deflate += deflate
@@ -172,19 +196,29 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                 for dst, src, n in all_copies:
                     h.d2d_async(dst, src, n, handle)
 
+            # the shards' column decodes share ONE launch too, queued
+            # behind the decompression on the job's stream
+            launch = None
+            if decodes:
+                from .formats.parquet import DecodeLaunch
+
+                launch = DecodeLaunch(decodes)
             job = ZstdJob(all_frames, pre_launch=pre, window=16 << 10,
                           snappy_frames=all_snappy,
                           deflate_frames=all_deflate,
-                          lz4_frames=all_lz4)
+                          lz4_frames=all_lz4,
+                          post_launch=launch.post if launch else None)
             for (f, lo, n, slo, sn, dlo, dn, llo, ln, ring,
-                 spans) in entries:
+                 spans, decode) in entries:
                 out.append((f, job.view(lo, n, slo, sn, dlo, dn,
                                         llo, ln),
-                            ring, spans))
+                            ring, spans,
+                            (launch, decode) if decode else None))
         return out
 
     def finish(item):
-        shard, job, data, spans = item
+        shard, job, data, spans, decoding = item
+        cols = None
         if job is not None:
             results = job.wait()
             bad = [(i, r) for i, r in enumerate(results) if not r.ok]
@@ -193,10 +227,17 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                     f"GPU decompress of {shard.name} failed: {bad[:3]}")
             import torch
 
+            if decoding is not None:
+                launch, decode = decoding
+                try:
+                    cols = decode.finish(launch.results(decode))
+                except IOError as e:
+                    raise IOError(f"{shard.name}: {e}") from None
             data = torch.from_dlpack(data.to_dlpack())
         log.info("dataset shard %s: %d spans, %d bytes decompressed",
                  shard.name, len(spans), int(data.numel()))
-        return ShardBatch(name=shard.name, data=data, spans=spans)
+        return ShardBatch(name=shard.name, data=data, spans=spans,
+                          columns=cols)
 
     # pending holds the PulledFile too: its HBM blob must stay alive
     # until the decode kernel reading it has finished

@@ -114,7 +114,9 @@ class ZstdJob:
     occupancy high even when each batch alone has fewer frames than the
     chip has wave slots.  pre_launch(stream_handle), when given, queues
     extra async work (device copies) on the same stream before the
-    kernels.  snappy_frames run through the snappy kernel on the same
+    kernels; post_launch(stream_handle) mirrors it after them (work
+    that consumes the decompressed bytes, e.g. the parquet column
+    decode).  snappy_frames run through the snappy kernel on the same
     stream (parquet's default page codec); their results surface as
     .snappy_results after wait()."""
 
@@ -125,7 +127,7 @@ class ZstdJob:
                  deflate_frames: list[tuple[int, int, int, int]] | None
                  = None,
                  lz4_frames: list[tuple[int, int, int, int]] | None
-                 = None):
+                 = None, post_launch=None):
         from ...gpu import hip
 
         h = hip()
@@ -191,6 +193,8 @@ class ZstdJob:
             h.zstd_frames(self._dbuf.ptr, n, self._s.handle,
                           window=window)
             h.d2h_async(addr, self._dbuf.ptr, nd, self._s.handle)
+        if post_launch is not None:
+            post_launch(self._s.handle)
         self._ev = h.Event()
         self._ev.record(self._s.handle)
 
