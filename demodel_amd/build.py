@@ -7,9 +7,10 @@ Two extensions, built straight with the toolchain (no setuptools overhead),
   host zstd, the GIL-free socket loops of csrc/sock_io.h).
   Plain C++, no torch, builds and runs anywhere.
 * ``demodel_amd/_hip.so``     — the GPU pipeline: pinned-ring allocator,
-  HIP streams/events, and the CDNA4 kernels (SHA-256, inflate, scatter,
-  GGUF and FP8 dequant, parquet page decode).  Compiled with hipcc for gfx950 only; importable
-  on a CPU-only box (calls fail until a GPU is present).
+  HIP streams/events, and the CDNA4 kernels (SHA-256, scatter, GGUF and
+  FP8 dequant, the zstd / snappy / inflate / LZ4 page codecs, parquet
+  page decode).  Compiled with hipcc for gfx950 only; importable on a
+  CPU-only box (calls fail until a GPU is present).
 """
 
 from __future__ import annotations
@@ -47,16 +48,31 @@ def _run(cmd: list[str]) -> None:
     subprocess.run(cmd, check=True)
 
 
-# in-tree headers of _native.so (rebuild triggers)
-NATIVE_HDRS = [os.path.join(CSRC, "sock_io.h")]
+NATIVE_SRCS = ["certs.cpp", "zstd_host.cpp", "sock_native.cpp"]
+
+# in-tree headers each source includes (rebuild triggers); every source
+# of NATIVE_SRCS and HIP_SRCS lists all of its own
+HDRS = {
+    "zstd_host.cpp": ["zstd_common.h"],
+    "sock_native.cpp": ["sock_io.h"],
+    "hip_core.cpp": ["resource_cache.h", "sock_io.h"],
+    "zstd_kernel.hip": ["zstd_common.h"],
+    "inflate.hip": ["lz_window.h"],
+    "snappy.hip": ["lz_window.h"],
+    "lz4.hip": ["lz_window.h"],
+}
+
+
+def _with_hdrs(src: str) -> list[str]:
+    """A source's path followed by its in-tree headers' paths."""
+    return [os.path.join(CSRC, f) for f in [src] + HDRS.get(src, [])]
 
 
 def build_native(force: bool = False) -> str:
     out = os.path.join(PKG_DIR, "_native.so")
-    srcs = [os.path.join(CSRC, "certs.cpp"),
-            os.path.join(CSRC, "zstd_host.cpp"),
-            os.path.join(CSRC, "sock_native.cpp")]
-    if not force and _newer(out, srcs + NATIVE_HDRS):
+    srcs = [os.path.join(CSRC, s) for s in NATIVE_SRCS]
+    if not force and _newer(out, [p for s in NATIVE_SRCS
+                                  for p in _with_hdrs(s)]):
         return out
     cmd = (
         ["c++", "-O2", "-std=c++17", "-shared", "-fPIC",
@@ -83,30 +99,20 @@ HIP_SRCS = [
 ]
 
 
-# in-tree headers a source includes (rebuild triggers)
-HIP_HDRS = {
-    "hip_core.cpp": [os.path.join(CSRC, "resource_cache.h"),
-                     os.path.join(CSRC, "sock_io.h")],
-}
-
-
 def build_hip(force: bool = False) -> str:
     out = os.path.join(PKG_DIR, "_hip.so")
-    srcs = [os.path.join(CSRC, s) for s in HIP_SRCS
-            if os.path.exists(os.path.join(CSRC, s))]
-    if not srcs:
+    names = [s for s in HIP_SRCS if os.path.exists(os.path.join(CSRC, s))]
+    if not names:
         raise RuntimeError("no HIP sources present")
-    hdrs = [p for ps in HIP_HDRS.values() for p in ps]
-    if not force and _newer(out, srcs + hdrs):
+    if not force and _newer(out, [p for s in names for p in _with_hdrs(s)]):
         return out
     hipcc = os.environ.get("HIPCC", "hipcc")
     objs = []
     os.makedirs(os.path.join(PKG_DIR, "_build"), exist_ok=True)
-    for src in srcs:
-        obj = os.path.join(
-            PKG_DIR, "_build", os.path.basename(src).rsplit(".", 1)[0] + ".o"
-        )
-        if not _newer(obj, [src] + HIP_HDRS.get(os.path.basename(src), [])):
+    for name in names:
+        src = os.path.join(CSRC, name)
+        obj = os.path.join(PKG_DIR, "_build", name.rsplit(".", 1)[0] + ".o")
+        if not _newer(obj, _with_hdrs(name)):
             cmd = (
                 [hipcc, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17",
                  "-fPIC", "-fvisibility=hidden", "-c", src, "-o", obj]

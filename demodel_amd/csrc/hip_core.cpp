@@ -65,8 +65,8 @@ void fp8_block_dequant_pass_limits(int64_t* out);
 void launch_gguf_dequant(int qtype, const void* src, uint16_t* dst_bf16,
                          int64_t n_blocks, hipStream_t stream);
 void launch_inflate_streams(const uint64_t* desc, int n_streams,
-                            int* status, hipStream_t stream);
-void launch_zstd_frames(const uint64_t* desc, int n_frames, int* status,
+                            hipStream_t stream);
+void launch_zstd_frames(const uint64_t* desc, int n_frames,
                         hipStream_t stream, int window);
 void launch_snappy_streams(const uint64_t* desc, int n_streams,
                            hipStream_t stream);
@@ -755,7 +755,7 @@ PYBIND11_MODULE(_hip, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("inflate_streams",
         [](uintptr_t desc, int n_streams, uintptr_t stream) {
-          launch_inflate_streams((const uint64_t*)desc, n_streams, nullptr,
+          launch_inflate_streams((const uint64_t*)desc, n_streams,
                                  (hipStream_t)stream);
         },
         py::call_guard<py::gil_scoped_release>(),
@@ -763,7 +763,7 @@ PYBIND11_MODULE(_hip, m) {
         "dst, dst_cap, written, status, consumed, pad), wave per stream");
   m.def("zstd_frames",
         [](uintptr_t desc, int n_frames, uintptr_t stream, int window) {
-          launch_zstd_frames((const uint64_t*)desc, n_frames, nullptr,
+          launch_zstd_frames((const uint64_t*)desc, n_frames,
                              (hipStream_t)stream, window);
         },
         py::call_guard<py::gil_scoped_release>(), py::arg("desc"),

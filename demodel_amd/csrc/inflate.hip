@@ -18,27 +18,11 @@
 // bodies); within a stream DEFLATE remains serially entropy-coded
 // (SURVEY.md §7 hard part (a)).
 
-#include <hip/hip_runtime.h>
+#include "lz_window.h"
 
 namespace {
 
-enum {
-  INF_OK = 0,
-  INF_ERR_FORMAT = -2,
-  INF_ERR_OVERFLOW = -3,
-  INF_ERR_UNDERRUN = -4,
-};
-
-struct __align__(16) InflateDesc {
-  uint64_t src;
-  uint64_t src_len;
-  uint64_t dst;
-  uint64_t dst_cap;
-  uint64_t written;   // out
-  int64_t status;     // out
-  uint64_t consumed;  // out
-  uint64_t _pad1;
-};
+using namespace lzw;
 
 struct BitReader {
   const uint8_t* p;
@@ -198,7 +182,7 @@ __constant__ uint8_t kClOrder[19] = {
 #define LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
 __global__ void __launch_bounds__(64, 2)
-inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
+inflate_kernel(StreamDesc* __restrict__ descs, int n_streams) {
   __shared__ struct {
     HuffTable litlen_t;
     HuffTable dist_t;
@@ -210,7 +194,7 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
   int lane = threadIdx.x;
 
   for (int s = blockIdx.x; s < n_streams; s += gridDim.x) {
-    InflateDesc* d = &descs[s];
+    StreamDesc* d = &descs[s];
     const uint8_t* src = (const uint8_t*)d->src;
     uint8_t* out = (uint8_t*)d->dst;
 
@@ -218,26 +202,22 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
     BitReader br;
     br.init(src, d->src_len);
     uint64_t pos = 0;
-    int64_t status = INF_OK;
+    int64_t status = LZ_OK;
     bool done = false;
 
     while (!done) {
-      if (br.overran()) { status = INF_ERR_UNDERRUN; break; }
+      if (br.overran()) { status = LZ_ERR_UNDERRUN; break; }
       uint32_t bfinal = br.bit1();
       uint32_t btype = br.bits(2);
       if (btype == 0) {                                   // stored
         br.align_byte();
         uint32_t blen = br.bits(16);
         uint32_t nlen = br.bits(16);
-        if ((blen ^ 0xFFFFu) != nlen) { status = INF_ERR_FORMAT; break; }
+        if ((blen ^ 0xFFFFu) != nlen) { status = LZ_ERR_FORMAT; break; }
         uint64_t so = br.byte_pos();
-        if (so + blen > br.len) { status = INF_ERR_UNDERRUN; break; }
-        if (pos + blen > d->dst_cap) { status = INF_ERR_OVERFLOW; break; }
-        for (uint32_t i = lane; i < blen; i += 64) {
-          uint8_t v = src[so + i];
-          out[pos + i] = v;
-          sh.win[(pos + i) & DWMASK] = v;
-        }
+        if (so + blen > br.len) { status = LZ_ERR_UNDERRUN; break; }
+        if (pos + blen > d->dst_cap) { status = LZ_ERR_OVERFLOW; break; }
+        put_run<DWIN>(out, sh.win, pos, src + so, blen, lane);
         LGKM0();
         pos += blen;
         br.buf = 0;
@@ -246,7 +226,7 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
         if (bfinal) done = true;
         continue;
       }
-      if (btype == 3) { status = INF_ERR_FORMAT; break; }
+      if (btype == 3) { status = LZ_ERR_FORMAT; break; }
 
       // ---- table setup (redundant build; striped LUT fill) ---------
       bool okt = true;
@@ -265,7 +245,7 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
         for (int i = 0; i < hclen; ++i)
           cl_lens[kClOrder[i]] = (uint8_t)br.bits(3);
         if (!huff_build(&sh.dist_t, cl_lens, 19)) {  // dist as CL scratch
-          status = INF_ERR_FORMAT;
+          status = LZ_ERR_FORMAT;
           break;
         }
         int total = hlit + hdist;
@@ -292,7 +272,7 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
               huff_build(&sh.litlen_t, sh.lens_buf, hlit) &&
               huff_build(&sh.dist_t, sh.lens_buf + hlit, hdist);
       }
-      if (!okt) { status = INF_ERR_FORMAT; break; }
+      if (!okt) { status = LZ_ERR_FORMAT; break; }
       lut_build(sh.litlen_lut, &sh.litlen_t, sh.lens_buf, 288, lane);
       lut_build(sh.dist_lut, &sh.dist_t, sh.lens_buf, 30, lane);
       LGKM0();
@@ -320,11 +300,11 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
       while (true) {
         int sym = huff_decode_lut(&br, sh.litlen_lut, &sh.litlen_t);
         if (sym < 0 || br.overran()) {
-          status = br.overran() ? INF_ERR_UNDERRUN : INF_ERR_FORMAT;
+          status = br.overran() ? LZ_ERR_UNDERRUN : LZ_ERR_FORMAT;
           break;
         }
         if (sym < 256) {
-          if (pos >= d->dst_cap) { status = INF_ERR_OVERFLOW; break; }
+          if (pos >= d->dst_cap) { status = LZ_ERR_OVERFLOW; break; }
           if (lit_n == 0) lit_base = pos;
           if (lane == (int)lit_n) lit_pend = (uint8_t)sym;
           ++lit_n;
@@ -334,39 +314,20 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
         }
         if (sym == 256) break;  // end of block
         sym -= 257;
-        if (sym >= 29) { status = INF_ERR_FORMAT; break; }
+        if (sym >= 29) { status = LZ_ERR_FORMAT; break; }
         uint32_t mlen = kLenBase[sym] + br.bits(kLenExtra[sym]);
         int dsym = huff_decode_lut(&br, sh.dist_lut, &sh.dist_t);
-        if (dsym < 0 || dsym >= 30) { status = INF_ERR_FORMAT; break; }
+        if (dsym < 0 || dsym >= 30) { status = LZ_ERR_FORMAT; break; }
         uint32_t dist = kDistBase[dsym] + br.bits(kDistExtra[dsym]);
-        if (dist > pos) { status = INF_ERR_FORMAT; break; }
-        if (pos + mlen > d->dst_cap) { status = INF_ERR_OVERFLOW; break; }
+        if (dist > pos) { status = LZ_ERR_FORMAT; break; }
+        if (pos + mlen > d->dst_cap) { status = LZ_ERR_OVERFLOW; break; }
         flush_lits();  // the match may read the just-written window
         // every source byte is within DWIN -> always LDS
-        LGKM0();
-        if (dist >= mlen) {
-          for (uint32_t k = lane; k < mlen; k += 64) {
-            uint8_t v = sh.win[(pos + k - dist) & DWMASK];
-            out[pos + k] = v;
-            sh.win[(pos + k) & DWMASK] = v;
-          }
-        } else {
-          uint32_t copied = 0;
-          while (copied < mlen) {
-            uint32_t n = min(dist, mlen - copied);
-            for (uint32_t k = lane; k < n; k += 64) {
-              uint8_t v = sh.win[(pos + copied + k - dist) & DWMASK];
-              out[pos + copied + k] = v;
-              sh.win[(pos + copied + k) & DWMASK] = v;
-            }
-            LGKM0();
-            copied += n;
-          }
-        }
+        copy_match<DWIN, false>(out, sh.win, pos, dist, mlen, lane);
         pos += mlen;
       }
       flush_lits();  // trailing literals of the block
-      if (status != INF_OK) break;
+      if (status != LZ_OK) break;
       if (bfinal) done = true;
     }
 
@@ -382,10 +343,6 @@ inflate_kernel(InflateDesc* __restrict__ descs, int n_streams) {
 }  // namespace
 
 extern "C" void launch_inflate_streams(const uint64_t* desc, int n_streams,
-                                       int* /*status_unused*/,
                                        hipStream_t stream) {
-  if (n_streams <= 0) return;
-  int blocks = n_streams < 4096 ? n_streams : 4096;
-  hipLaunchKernelGGL(inflate_kernel, dim3(blocks), dim3(64), 0, stream,
-                     (InflateDesc*)desc, n_streams);
+  launch_streams(inflate_kernel, desc, n_streams, stream);
 }

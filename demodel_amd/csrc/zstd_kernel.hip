@@ -817,7 +817,7 @@ zstd_kernel_x2(ZstdDesc* __restrict__ descs, int n_streams) {
 }  // namespace
 
 extern "C" void launch_zstd_frames(const uint64_t* desc, int n_frames,
-                                   int* /*unused*/, hipStream_t stream,
+                                   hipStream_t stream,
                                    int window /*0=auto,16384,65536*/) {
   if (n_frames <= 0) return;
   // both windows are CORRECT for any match distance (exec_seq falls

@@ -7,11 +7,11 @@ a training/ingest loop can consume while later shards still pull.
 
 Overlap is two-level: the pull runs on worker threads (pull_hf_stream)
 while this thread LAUNCHES each completed shard's decompression async on
-its own HIP stream (ZstdJob), so downloads, several shards' decodes, and
-the consumer all run concurrently.  Per-shard frame counts are far below
-the chip's wave capacity (256 frames vs 2048 wave slots), so concurrent
-per-shard launches are what keep the zstd kernel occupancy at the level
-a single whole-dataset launch would get.
+its own HIP stream (DecompressJob), so downloads, several shards'
+decodes, and the consumer all run concurrently.  Per-shard frame counts
+are far below the chip's wave capacity (256 frames vs 2048 wave slots),
+so concurrent per-shard launches are what keep the zstd kernel occupancy
+at the level a single whole-dataset launch would get.
 
 On CPU-only machines the same API decompresses with pyarrow, so the data
 path is testable anywhere.
@@ -43,36 +43,36 @@ class ShardBatch:
 
 
 def _prep_parquet_gpu(blob, columns=None):
-    """prep_pages_gpu's plan plus, when columns is not None, the
-    ColumnDecode that turns the decompressed pages into tensors."""
+    """(prep_pages_gpu's plan, decode): decode is the ColumnDecode that
+    turns the decompressed pages into tensors when columns is not None,
+    else None."""
     from .formats import parquet as pqf
 
     if columns is None:
-        return pqf.prep_pages_gpu(blob, pqf.blob_pages(blob)) + (None,)
+        return pqf.prep_pages_gpu(blob, pqf.blob_pages(blob)), None
     meta, chunk_pages = pqf.blob_meta_pages(blob)
     plan = pqf.plan_columns(meta, chunk_pages, columns)
     pages = [(cm.codec, info)
              for cm, cp in zip(meta.chunks, chunk_pages) for info in cp]
     prep = pqf.prep_pages_gpu(blob, pages)
-    ring, spans = prep[5], prep[6]
-    return prep + (pqf.ColumnDecode(plan, ring.ptr, spans.__getitem__),)
+    return prep, pqf.ColumnDecode(plan, prep.ring.ptr,
+                                  prep.spans.__getitem__)
 
 
 def _prep_zst_frames_gpu(blob, idx):
     from ..gpu import hip
+    from .formats.compress import DecompressPlan
 
-    h = hip()
     total = sum(fr["decompressed"] for fr in idx["frames"])
-    ring = h.DeviceBuffer(max(total, 1))
-    frames = []
-    spans = []
+    plan = DecompressPlan(ring=hip().DeviceBuffer(max(total, 1)))
     off = 0
     for fr in idx["frames"]:
-        frames.append((blob.buffer.ptr + fr["offset"], fr["compressed"],
-                       ring.ptr + off, fr["decompressed"]))
-        spans.append((off, fr["decompressed"]))
+        plan.streams["zstd"].append(
+            (blob.buffer.ptr + fr["offset"], fr["compressed"],
+             plan.ring.ptr + off, fr["decompressed"]))
+        plan.spans.append((off, fr["decompressed"]))
         off += fr["decompressed"]
-    return frames, [], [], [], [], ring, spans
+    return plan
 
 
 def _decompress_cpu(blob, idx):
@@ -130,6 +130,7 @@ def stream_dataset(repo: str, endpoint: str | None = None,
     last shard lands — best whole-dataset seconds-to-ready."""
     from ..gpu import have_gpu
 
+    from .formats.compress import check_results
     from .pull import pull_hf_stream
 
     _, names, gen = pull_hf_stream(
@@ -142,23 +143,18 @@ def stream_dataset(repo: str, endpoint: str | None = None,
 
     def launch_batch(shards):
         """Coalesce every shard that became ready at the same time into
-        ONE kernel launch (a shared ZstdJob; each shard holds a frame-
-        range view).  Per-shard frame counts (~hundreds) are far below
-        the chip's wave slots, and kernels on the same HW queue
+        ONE launch per codec (a shared DecompressJob; each shard holds a
+        view of its ranges).  Per-shard frame counts (~hundreds) are far
+        below the chip's wave slots, and kernels on the same HW queue
         serialize — batching restores big-launch occupancy while the
         launch itself stays async.  Returns [(shard, jobview_or_None,
         ring_or_data, spans)].  The torch wrap of a GPU ring happens at
         FINISH time: torch.from_dlpack synchronizes with the device,
         which would serialize the launches."""
-        from ..gpu import hip
-        from .formats.compress import ZstdJob
+        from .formats.compress import DecompressJob, DecompressPlan
 
         out = []
-        all_frames = []
-        all_snappy = []
-        all_deflate = []
-        all_lz4 = []
-        all_copies = []
+        merged = DecompressPlan()
         decodes = []
         entries = []
         for f in shards:
@@ -167,35 +163,18 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                     raise RuntimeError(
                         "parquet streaming needs a GPU (CPU fallback "
                         "covers .zst shards)")
-                (frames, snappy, deflate, lz4, copies, ring,
-                 spans, decode) = _prep_parquet_gpu(f.blob, columns)
+                plan, decode = _prep_parquet_gpu(f.blob, columns)
             else:
                 idx = _sidecar_idx(f.sidecar)
                 if not gpu:
                     data, spans = _decompress_cpu(f.blob, idx)
                     out.append((f, None, data, spans, None))
                     continue
-                (frames, snappy, deflate, lz4, copies, ring,
-                 spans) = _prep_zst_frames_gpu(f.blob, idx)
-                decode = None
-            entries.append((f, len(all_frames), len(frames),
-                            len(all_snappy), len(snappy),
-                            len(all_deflate), len(deflate),
-                            len(all_lz4), len(lz4), ring, spans, decode))
+                plan, decode = _prep_zst_frames_gpu(f.blob, idx), None
+            entries.append((f, merged.absorb(plan), plan, decode))
             if decode is not None:
                 decodes.append(decode)
-            all_frames += frames
-            all_snappy += snappy
-            all_deflate += deflate
-            all_lz4 += lz4
-            all_copies += copies
         if entries:
-            h = hip()
-
-            def pre(handle):
-                for dst, src, n in all_copies:
-                    h.d2d_async(dst, src, n, handle)
-
             # the shards' column decodes share ONE launch too, queued
             # behind the decompression on the job's stream
             launch = None
@@ -203,16 +182,12 @@ def stream_dataset(repo: str, endpoint: str | None = None,
                 from .formats.parquet import DecodeLaunch
 
                 launch = DecodeLaunch(decodes)
-            job = ZstdJob(all_frames, pre_launch=pre, window=16 << 10,
-                          snappy_frames=all_snappy,
-                          deflate_frames=all_deflate,
-                          lz4_frames=all_lz4,
-                          post_launch=launch.post if launch else None)
-            for (f, lo, n, slo, sn, dlo, dn, llo, ln, ring,
-                 spans, decode) in entries:
-                out.append((f, job.view(lo, n, slo, sn, dlo, dn,
-                                        llo, ln),
-                            ring, spans,
+            job = DecompressJob(
+                merged.streams, pre_launch=merged.queue_copies,
+                window=16 << 10,
+                post_launch=launch.post if launch else None)
+            for f, ranges, plan, decode in entries:
+                out.append((f, job.view(ranges), plan.ring, plan.spans,
                             (launch, decode) if decode else None))
         return out
 
@@ -220,11 +195,7 @@ def stream_dataset(repo: str, endpoint: str | None = None,
         shard, job, data, spans, decoding = item
         cols = None
         if job is not None:
-            results = job.wait()
-            bad = [(i, r) for i, r in enumerate(results) if not r.ok]
-            if bad:
-                raise IOError(
-                    f"GPU decompress of {shard.name} failed: {bad[:3]}")
+            check_results(job.wait(), f"GPU decompress of {shard.name}")
             import torch
 
             if decoding is not None:

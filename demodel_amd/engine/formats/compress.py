@@ -1,18 +1,21 @@
-"""GPU decompression front-end: gzip containers + raw DEFLATE streams.
+"""GPU decompression front-end: zstd, snappy, raw DEFLATE (gzip) and LZ4.
 
-Drives csrc/inflate.hip (wave-per-stream DEFLATE) over batches of
-compressed regions already resident in HBM: cached response bodies in
-their original Content-Encoding (reference CONTRIBUTING.md:116), gzip
-members of dataset streams, parquet page payloads.
+Drives the wave-per-stream kernels (csrc/zstd_kernel.hip, snappy.hip,
+inflate.hip, lz4.hip) over batches of compressed regions already
+resident in HBM: cached response bodies in their original
+Content-Encoding (reference CONTRIBUTING.md:116), gzip members and zstd
+frames of dataset streams, parquet page payloads.  One DecompressJob
+runs any mix of the codecs on one stream.
 """
 
 from __future__ import annotations
 
 import ctypes
 import struct
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
-DESC_WORDS = 8  # u64s per InflateDesc
+DESC_WORDS = 8  # u64s per stream descriptor (csrc/lz_window.h)
+ZSTD_WS_BYTES = 144 << 10
 
 ERR = {0: "ok", -1: "magic", -2: "format", -3: "overflow",
        -4: "underrun", -5: "dictionary-unsupported"}
@@ -53,235 +56,207 @@ class InflateResult:
         return None if self.ok else ERR.get(self.status, str(self.status))
 
 
-def inflate_gpu(streams: list[tuple[int, int, int, int]],
-                stream_handle=None) -> list[InflateResult]:
-    """Inflate raw DEFLATE streams on the GPU.
-
-    streams: (src_ptr, src_len, dst_ptr, dst_cap) device addresses.
-    Returns per-stream InflateResult; raises on any failed stream only if
-    the caller doesn't inspect (callers should check .ok).
-    """
-    from ...gpu import hip
-
-    h = hip()
-    n = len(streams)
-    if n == 0:
-        return []
-    own = stream_handle is None
-    s = h.Stream(0) if own else None
-    handle = s.handle if own else stream_handle
-    desc = bytearray(n * DESC_WORDS * 8)
+def pack_descs(desc, streams, ws_ptr: int = 0) -> None:
+    """Write one 8-u64 descriptor per (src, len, dst, cap) stream into
+    the writable buffer desc.  ws_ptr, when non-zero, is the base of a
+    workspace of ZSTD_WS_BYTES per stream; each stream's share goes in
+    word 7 (zstd), which the other kernels ignore."""
     for i, (src, slen, dst, cap) in enumerate(streams):
         struct.pack_into("<8Q", desc, i * DESC_WORDS * 8,
-                         src, slen, dst, cap, 0, 0, 0, 0)
-    dbuf = h.DeviceBuffer(len(desc))
-    carr = (ctypes.c_char * len(desc)).from_buffer(desc)
-    h.h2d_async(dbuf.ptr, ctypes.addressof(carr), len(desc), handle)
-    h.inflate_streams(dbuf.ptr, n, handle)
-    h.d2h_async(ctypes.addressof(carr), dbuf.ptr, len(desc), handle)
-    if own:
-        s.sync()
-    else:
-        h.device_sync()
+                         src, slen, dst, cap, 0, 0, 0,
+                         ws_ptr + i * ZSTD_WS_BYTES if ws_ptr else 0)
+
+
+def parse_results(desc, n: int) -> list[InflateResult]:
+    """The (written, status, consumed) words the kernel left in each of
+    n descriptors; status is a signed int64."""
     out = []
     for i in range(n):
-        vals = struct.unpack_from("<8Q", desc, i * DESC_WORDS * 8)
-        written, status_u, consumed = vals[4], vals[5], vals[6]
-        status = status_u - (1 << 64) if status_u >= (1 << 63) else status_u
-        out.append(InflateResult(written=written, status=int(status),
+        written, status, consumed = struct.unpack_from(
+            "<QqQ", desc, (i * DESC_WORDS + 4) * 8)
+        out.append(InflateResult(written=written, status=status,
                                  consumed=consumed))
     return out
 
 
-ZSTD_WS_BYTES = 144 << 10
+def check_results(results, what: str = "GPU page decompress") -> None:
+    bad = [(i, r) for i, r in enumerate(results) if not r.ok]
+    if bad:
+        raise IOError(f"{what} failed: {bad[:3]}")
 
 
-def _parse_results(desc: bytearray, n: int) -> list[InflateResult]:
-    out = []
-    for i in range(n):
-        vals = struct.unpack_from("<8Q", desc, i * DESC_WORDS * 8)
-        written, status_u, consumed = vals[4], vals[5], vals[6]
-        status = status_u - (1 << 64) if status_u >= (1 << 63) else status_u
-        out.append(InflateResult(written=written, status=int(status),
-                                 consumed=consumed))
-    return out
+# codec -> its _hip launch; the order is the order of a job's results
+CODECS = {
+    "zstd": lambda h, desc, n, stream, window:
+        h.zstd_frames(desc, n, stream, window=window),
+    "snappy": lambda h, desc, n, stream, window:
+        h.snappy_streams(desc, n, stream),
+    "deflate": lambda h, desc, n, stream, window:
+        h.inflate_streams(desc, n, stream),
+    "lz4": lambda h, desc, n, stream, window:
+        h.lz4_streams(desc, n, stream),
+}
 
 
-class ZstdJob:
+class DecompressJob:
     """An in-flight GPU decompression batch on its own HIP stream: the
     launch returns immediately so several batches (e.g. dataset shards
     landing at different times) decode CONCURRENTLY, which keeps wave
     occupancy high even when each batch alone has fewer frames than the
-    chip has wave slots.  pre_launch(stream_handle), when given, queues
-    extra async work (device copies) on the same stream before the
-    kernels; post_launch(stream_handle) mirrors it after them (work
+    chip has wave slots.  streams maps a codec of CODECS to its
+    (src_ptr, src_len, dst_ptr, dst_cap) device regions; each non-empty
+    codec is one kernel launch.  pre_launch(stream_handle), when given,
+    queues extra async work (device copies) on the same stream before
+    the kernels; post_launch(stream_handle) mirrors it after them (work
     that consumes the decompressed bytes, e.g. the parquet column
-    decode).  snappy_frames run through the snappy kernel on the same
-    stream (parquet's default page codec); their results surface as
-    .snappy_results after wait()."""
+    decode).  window selects the zstd kernel's LDS window."""
 
-    def __init__(self, frames: list[tuple[int, int, int, int]],
-                 pre_launch=None, window: int = 0,
-                 snappy_frames: list[tuple[int, int, int, int]] | None
-                 = None,
-                 deflate_frames: list[tuple[int, int, int, int]] | None
-                 = None,
-                 lz4_frames: list[tuple[int, int, int, int]] | None
-                 = None, post_launch=None):
+    def __init__(self, streams: dict[str, list[tuple[int, int, int, int]]],
+                 pre_launch=None, post_launch=None, window: int = 0):
         from ...gpu import hip
 
+        unknown = set(streams) - set(CODECS)
+        if unknown:
+            raise ValueError(f"unknown codec(s) {sorted(unknown)}")
         h = hip()
-        n = self._n = len(frames)
-        sn = self._sn = len(snappy_frames or ())
-        dn = self._dn = len(deflate_frames or ())
-        ln = self._ln = len(lz4_frames or ())
         self._s = h.Stream(0)
+        self._slabs = {}     # codec -> (pinned slab, n, device buffers)
+        self._results = None
         if pre_launch is not None:
             pre_launch(self._s.handle)
-        if dn:
-            nd = dn * DESC_WORDS * 8
-            self._dpin = h.PinnedPool(nd, 1)
-            ddesc = self._dpin.slab_view(0)
-            for i, (src, slen, dst, cap) in enumerate(deflate_frames):
-                struct.pack_into("<8Q", ddesc, i * DESC_WORDS * 8,
-                                 src, slen, dst, cap, 0, 0, 0, 0)
-            self._ddbuf = h.DeviceBuffer(nd)
-            addr = self._dpin.slab_ptr(0)
-            h.h2d_async(self._ddbuf.ptr, addr, nd, self._s.handle)
-            h.inflate_streams(self._ddbuf.ptr, dn, self._s.handle)
-            h.d2h_async(addr, self._ddbuf.ptr, nd, self._s.handle)
-        if ln:
-            nd = ln * DESC_WORDS * 8
-            self._lpin = h.PinnedPool(nd, 1)
-            ldesc = self._lpin.slab_view(0)
-            for i, (src, slen, dst, cap) in enumerate(lz4_frames):
-                struct.pack_into("<8Q", ldesc, i * DESC_WORDS * 8,
-                                 src, slen, dst, cap, 0, 0, 0, 0)
-            self._ldbuf = h.DeviceBuffer(nd)
-            addr = self._lpin.slab_ptr(0)
-            h.h2d_async(self._ldbuf.ptr, addr, nd, self._s.handle)
-            h.lz4_streams(self._ldbuf.ptr, ln, self._s.handle)
-            h.d2h_async(addr, self._ldbuf.ptr, nd, self._s.handle)
-        if sn:
-            nd = sn * DESC_WORDS * 8
-            self._spin = h.PinnedPool(nd, 1)
-            sdesc = self._spin.slab_view(0)
-            for i, (src, slen, dst, cap) in enumerate(snappy_frames):
-                struct.pack_into("<8Q", sdesc, i * DESC_WORDS * 8,
-                                 src, slen, dst, cap, 0, 0, 0, 0)
-            self._sdbuf = h.DeviceBuffer(nd)
-            addr = self._spin.slab_ptr(0)
-            h.h2d_async(self._sdbuf.ptr, addr, nd, self._s.handle)
-            h.snappy_streams(self._sdbuf.ptr, sn, self._s.handle)
-            h.d2h_async(addr, self._sdbuf.ptr, nd, self._s.handle)
-        if n:
-            self._ws = h.DeviceBuffer(n * ZSTD_WS_BYTES)
-            nd = n * DESC_WORDS * 8
-            # PINNED staging for the descriptor block: hipMemcpyAsync
-            # to/from pageable memory BLOCKS the host thread until every
-            # prior op on the stream (the kernel!) completes, which would
-            # make this "async" launch synchronous
-            self._pin = h.PinnedPool(nd, 1)
-            desc = self._pin.slab_view(0)
-            for i, (src, slen, dst, cap) in enumerate(frames):
-                struct.pack_into("<8Q", desc, i * DESC_WORDS * 8,
-                                 src, slen, dst, cap, 0, 0, 0,
-                                 self._ws.ptr + i * ZSTD_WS_BYTES)
-            self._dbuf = h.DeviceBuffer(nd)
-            addr = self._pin.slab_ptr(0)
-            h.h2d_async(self._dbuf.ptr, addr, nd, self._s.handle)
-            h.zstd_frames(self._dbuf.ptr, n, self._s.handle,
-                          window=window)
-            h.d2h_async(addr, self._dbuf.ptr, nd, self._s.handle)
+        for codec, launch in CODECS.items():
+            if streams.get(codec):
+                self._launch(h, codec, launch, streams[codec], window)
         if post_launch is not None:
             post_launch(self._s.handle)
         self._ev = h.Event()
         self._ev.record(self._s.handle)
 
+    def _launch(self, h, codec, launch, streams, window) -> None:
+        n = len(streams)
+        nd = n * DESC_WORDS * 8
+        handle = self._s.handle
+        ws = h.DeviceBuffer(n * ZSTD_WS_BYTES) if codec == "zstd" else None
+        # PINNED staging for the descriptor block: hipMemcpyAsync
+        # to/from pageable memory BLOCKS the host thread until every
+        # prior op on the stream (the kernel!) completes, which would
+        # make this "async" launch synchronous
+        pin = h.PinnedPool(nd, 1)
+        pack_descs(pin.slab_view(0), streams, ws.ptr if ws else 0)
+        dbuf = h.DeviceBuffer(nd)
+        addr = pin.slab_ptr(0)
+        h.h2d_async(dbuf.ptr, addr, nd, handle)
+        launch(h, dbuf.ptr, n, handle, window)
+        h.d2h_async(addr, dbuf.ptr, nd, handle)
+        self._slabs[codec] = (pin, n, dbuf, ws)
+
     def done(self) -> bool:
         return self._ev.query()
 
-    def wait(self) -> list[InflateResult]:
-        if not hasattr(self, "_results"):
+    def results(self, codec: str) -> list[InflateResult]:
+        """One codec's results, in the order its streams were given."""
+        if self._results is None:
             self._s.sync()
-            self._results = (_parse_results(
-                bytearray(self._pin.slab_view(0)), self._n)
-                if self._n else [])
-            self.snappy_results = (_parse_results(
-                bytearray(self._spin.slab_view(0)), self._sn)
-                if self._sn else [])
-            self.deflate_results = (_parse_results(
-                bytearray(self._dpin.slab_view(0)), self._dn)
-                if self._dn else [])
-            self.lz4_results = (_parse_results(
-                bytearray(self._lpin.slab_view(0)), self._ln)
-                if self._ln else [])
-        return self._results
+            self._results = {
+                c: parse_results(pin.slab_view(0), n)
+                for c, (pin, n, _, _) in self._slabs.items()}
+        return self._results.get(codec, [])
 
-    def view(self, lo: int, n: int, slo: int = 0, sn: int = 0,
-             dlo: int = 0, dn: int = 0, llo: int = 0,
-             ln: int = 0) -> "ZstdJobView":
-        return ZstdJobView(self, lo, n, slo, sn, dlo, dn, llo, ln)
+    def wait(self) -> list[InflateResult]:
+        """Every result, codec by codec in CODECS order."""
+        return [r for codec in CODECS for r in self.results(codec)]
+
+    def view(self, ranges: dict[str, tuple[int, int]]) -> "JobView":
+        return JobView(self, ranges)
 
 
-class ZstdJobView:
-    """A frame-range of a (possibly shared) ZstdJob — several shards
-    coalesced into ONE launch each hold a view of it.  wait() returns
-    this view's zstd results followed by its snappy results."""
+class JobView:
+    """Per-codec ranges {codec: (lo, n)} of a (possibly shared)
+    DecompressJob — several shards coalesced into ONE launch each hold
+    a view of it.  wait() returns this view's results codec by codec in
+    CODECS order."""
 
-    def __init__(self, job: ZstdJob, lo: int, n: int, slo: int = 0,
-                 sn: int = 0, dlo: int = 0, dn: int = 0,
-                 llo: int = 0, ln: int = 0):
-        self._job, self._lo, self._vn = job, lo, n
-        self._slo, self._svn = slo, sn
-        self._dlo, self._dvn = dlo, dn
-        self._llo, self._lvn = llo, ln
+    def __init__(self, job, ranges: dict[str, tuple[int, int]]):
+        self._job, self._ranges = job, ranges
 
     def done(self) -> bool:
         return self._job.done()
 
     def wait(self) -> list[InflateResult]:
-        res = self._job.wait()[self._lo:self._lo + self._vn]
-        if self._svn:
-            res = res + self._job.snappy_results[
-                self._slo:self._slo + self._svn]
-        if self._dvn:
-            res = res + self._job.deflate_results[
-                self._dlo:self._dlo + self._dvn]
-        if self._lvn:
-            res = res + self._job.lz4_results[
-                self._llo:self._llo + self._lvn]
+        res = []
+        for codec in CODECS:
+            lo, n = self._ranges.get(codec, (0, 0))
+            if n:
+                res += self._job.results(codec)[lo:lo + n]
         return res
 
 
-def zstd_gpu(frames: list[tuple[int, int, int, int]],
-             stream_handle=None, window: int = 0) -> list[InflateResult]:
-    """Decompress zstd frames on the GPU (csrc/zstd_kernel.hip).
+@dataclass
+class DecompressPlan:
+    """What one DecompressJob is to do for a landed blob: streams per
+    codec, (dst, src, n) device copies for what is stored uncompressed,
+    the HBM ring everything lands in and the (offset, size) span of each
+    unit (page, frame) in it."""
+    streams: dict = field(
+        default_factory=lambda: {codec: [] for codec in CODECS})
+    copies: list = field(default_factory=list)
+    ring: object = None
+    spans: list = field(default_factory=list)
 
-    frames: (src_ptr, src_len, dst_ptr, dst_cap) device addresses.
-    A 144 KiB workspace per frame is allocated here.
-    """
-    from ...gpu import hip
+    def queue_copies(self, stream_handle) -> None:
+        """The job's pre_launch hook: the copies, async on its stream."""
+        from ...gpu import hip
 
-    n = len(frames)
-    if n == 0:
+        h = hip()
+        for dst, src, n in self.copies:
+            h.d2d_async(dst, src, n, stream_handle)
+
+    def absorb(self, other: "DecompressPlan") -> dict[str, tuple[int, int]]:
+        """Append other's streams and copies (ring and spans stay its
+        own); returns where they went as {codec: (lo, n)}, which is what
+        a view of the merged job takes."""
+        ranges = {}
+        for codec, mine in self.streams.items():
+            theirs = other.streams.get(codec, [])
+            ranges[codec] = (len(mine), len(theirs))
+            mine += theirs
+        self.copies += other.copies
+        return ranges
+
+
+def _decompress(codec: str, streams, window: int = 0):
+    if not streams:
         return []
-    if stream_handle is None:
-        return ZstdJob(frames, window=window).wait()
-    h = hip()
-    ws = h.DeviceBuffer(n * ZSTD_WS_BYTES)
-    desc = bytearray(n * DESC_WORDS * 8)
-    for i, (src, slen, dst, cap) in enumerate(frames):
-        struct.pack_into("<8Q", desc, i * DESC_WORDS * 8,
-                         src, slen, dst, cap, 0, 0, 0,
-                         ws.ptr + i * ZSTD_WS_BYTES)
-    dbuf = h.DeviceBuffer(len(desc))
-    carr = (ctypes.c_char * len(desc)).from_buffer(desc)
-    h.h2d_async(dbuf.ptr, ctypes.addressof(carr), len(desc), stream_handle)
-    h.zstd_frames(dbuf.ptr, n, stream_handle, window=window)
-    h.d2h_async(ctypes.addressof(carr), dbuf.ptr, len(desc), stream_handle)
-    h.device_sync()
-    return _parse_results(desc, n)
+    return DecompressJob({codec: streams}, window=window).wait()
+
+
+def inflate_gpu(streams: list[tuple[int, int, int, int]]
+                ) -> list[InflateResult]:
+    """Inflate raw DEFLATE streams on the GPU (csrc/inflate.hip).
+
+    streams: (src_ptr, src_len, dst_ptr, dst_cap) device addresses.
+    Returns per-stream InflateResult; callers check .ok."""
+    return _decompress("deflate", streams)
+
+
+def zstd_gpu(frames: list[tuple[int, int, int, int]],
+             window: int = 0) -> list[InflateResult]:
+    """Decompress zstd frames on the GPU (csrc/zstd_kernel.hip); the
+    job allocates the 144 KiB workspace each frame needs."""
+    return _decompress("zstd", frames, window)
+
+
+def lz4_gpu(streams: list[tuple[int, int, int, int]]
+            ) -> list[InflateResult]:
+    """Decompress raw LZ4 blocks on the GPU (csrc/lz4.hip) — parquet's
+    LZ4/LZ4_RAW page codecs."""
+    return _decompress("lz4", streams)
+
+
+def snappy_gpu(streams: list[tuple[int, int, int, int]]
+               ) -> list[InflateResult]:
+    """Decompress raw snappy streams on the GPU (csrc/snappy.hip)."""
+    return _decompress("snappy", streams)
 
 
 def gunzip_blob_gpu(blob, out_size: int | None = None):
@@ -315,24 +290,3 @@ def gunzip_blob_gpu(blob, out_size: int | None = None):
             continue
         raise IOError(f"GPU inflate failed: {res.error}")
     raise IOError("GPU inflate: capacity growth exhausted")
-
-
-def lz4_gpu(streams: list[tuple[int, int, int, int]]
-            ) -> list[InflateResult]:
-    """Decompress raw LZ4 blocks on the GPU (csrc/lz4.hip) — parquet's
-    LZ4/LZ4_RAW page codecs."""
-    job = ZstdJob([], lz4_frames=streams)
-    job.wait()
-    return job.lz4_results
-
-
-def snappy_gpu(streams: list[tuple[int, int, int, int]]
-               ) -> list[InflateResult]:
-    """Decompress raw snappy streams on the GPU (csrc/snappy.hip).
-
-    streams: (src_ptr, src_len, dst_ptr, dst_cap) device addresses."""
-    if not streams:
-        return []
-    job = ZstdJob([], snappy_frames=streams)
-    job.wait()
-    return job.snappy_results

@@ -632,23 +632,17 @@ def file_pages(path: str):
 
 
 def prep_pages_gpu(blob, pages, ring=None):
-    """Build the decode plan for a landed parquet blob's pages: returns
-    (frames, snappy, deflate, copies, ring, spans) — zstd / snappy /
-    raw-DEFLATE (gzip pages, member header parsed from PageInfo.head)
-    kernel inputs plus (dst, src, n) device copies for UNCOMPRESSED
-    pages and v2 level prefixes."""
+    """Build the DecompressPlan for a landed parquet blob's pages: zstd
+    / snappy / lz4 / raw-DEFLATE (gzip pages, member header parsed from
+    PageInfo.head) kernel inputs plus (dst, src, n) device copies for
+    UNCOMPRESSED pages and v2 level prefixes."""
     from ...gpu import hip
-    from .compress import gzip_deflate_offset
+    from .compress import DecompressPlan, gzip_deflate_offset
 
-    h = hip()
     total = sum(p.uncomp_size for _, p in pages)
-    ring = ring or h.DeviceBuffer(max(total, 1))
-    frames = []
-    snappy = []
-    deflate = []
-    lz4 = []
-    copies = []
-    spans = []
+    ring = ring or hip().DeviceBuffer(max(total, 1))
+    plan = DecompressPlan(ring=ring)
+    streams, copies = plan.streams, plan.copies
     off = 0
     for codec, p in pages:
         lvl = p.lvl_bytes
@@ -663,57 +657,46 @@ def prep_pages_gpu(blob, pages, ring=None):
         if not p.is_compressed or codec == CODEC_UNCOMPRESSED:
             copies.append((dst, src, clen))
         elif codec == CODEC_ZSTD:
-            frames.append((src, clen, dst, ulen))
+            streams["zstd"].append((src, clen, dst, ulen))
         elif codec == CODEC_SNAPPY:
-            snappy.append((src, clen, dst, ulen))
+            streams["snappy"].append((src, clen, dst, ulen))
         elif codec in (CODEC_LZ4, CODEC_LZ4_RAW):
-            lz4.append((src, clen, dst, ulen))
+            streams["lz4"].append((src, clen, dst, ulen))
         elif codec == CODEC_GZIP:
             gz = gzip_deflate_offset(p.head)
             # raw DEFLATE stream between the member header and the
             # 8-byte crc32+isize trailer
-            deflate.append((src + gz, clen - gz - 8, dst, ulen))
+            streams["deflate"].append((src + gz, clen - gz - 8, dst, ulen))
         else:
             raise ValueError(f"GPU path supports ZSTD/SNAPPY/GZIP/LZ4/"
                              f"UNCOMPRESSED, got codec {codec}")
-        spans.append((off, p.uncomp_size))
+        plan.spans.append((off, p.uncomp_size))
         off += p.uncomp_size
-    return frames, snappy, deflate, lz4, copies, ring, spans
+    return plan
 
 
 def launch_pages_gpu(blob, pages, ring=None):
-    """Queue GPU decompression of a landed parquet blob's ZSTD pages
-    into an HBM ring, ASYNC on the job's own stream.  Returns (job,
-    ring, spans); call job.wait() and check the results before reading
-    the ring."""
-    from ...gpu import hip
-    from .compress import ZstdJob
+    """Queue GPU decompression of a landed parquet blob's pages into an
+    HBM ring, ASYNC on the job's own stream.  Returns (job, ring,
+    spans); call job.wait() and check the results before reading the
+    ring."""
+    from .compress import DecompressJob
 
-    h = hip()
-    frames, snappy, deflate, lz4, copies, ring, spans = prep_pages_gpu(
-        blob, pages, ring)
-
-    def pre(handle):
-        for dst, src, n in copies:
-            h.d2d_async(dst, src, n, handle)
-
+    plan = prep_pages_gpu(blob, pages, ring)
     # 16 KiB LDS window: page batches run as concurrent jobs in
     # stream_dataset, so occupancy beats far-match locality
-    job = ZstdJob(frames, pre_launch=pre, window=16 << 10,
-                  snappy_frames=snappy, deflate_frames=deflate,
-                  lz4_frames=lz4)
-    return job, ring, spans
+    job = DecompressJob(plan.streams, pre_launch=plan.queue_copies,
+                        window=16 << 10)
+    return job, plan.ring, plan.spans
 
 
 def decompress_pages_gpu(blob, pages, ring=None):
     """Synchronous wrapper around launch_pages_gpu: returns
     (ring_buffer, [(out_offset, size)]) covering every page."""
+    from .compress import check_results
+
     job, ring, spans = launch_pages_gpu(blob, pages, ring)
-    results = (job.wait() + job.snappy_results + job.deflate_results
-               + job.lz4_results)
-    bad = [(i, r) for i, r in enumerate(results) if not r.ok]
-    if bad:
-        raise IOError(f"GPU page decompress failed: {bad[:3]}")
+    check_results(job.wait())
     return ring, spans
 
 
@@ -1053,7 +1036,7 @@ class ColumnDecode:
 
 class DecodeLaunch:
     """One parquet_decode launch over the descriptor rows of one or more
-    ColumnDecodes.  post(stream_handle) is a ZstdJob post_launch hook:
+    ColumnDecodes.  post(stream_handle) is a DecompressJob post_launch hook:
     pinned descriptor block up, kernel, block back, all on the stream
     that decompressed the pages."""
 
@@ -1124,10 +1107,8 @@ def launch_columns_gpu(blob, columns=None):
     then their decode, ASYNC on the job's own stream.  Returns (job,
     pending): job.wait(), check the decompression results, then
     pending.finish()."""
-    from ...gpu import hip
-    from .compress import ZstdJob
+    from .compress import DecompressJob
 
-    h = hip()
     meta, chunk_pages = blob_meta_pages(blob)
     plan = plan_columns(meta, chunk_pages, columns)   # raises before launch
     flat = [(cm.codec, info)
@@ -1135,20 +1116,13 @@ def launch_columns_gpu(blob, columns=None):
             for info in pages]
     need = sorted({i for col in plan.columns for p in col.pages
                    for i in (p.index, p.dict_index) if i >= 0})
-    frames, snappy, deflate, lz4, copies, ring, spans = prep_pages_gpu(
-        blob, [flat[i] for i in need])
-    where = dict(zip(need, spans))
-    decode = ColumnDecode(plan, ring.ptr, where.__getitem__)
+    prep = prep_pages_gpu(blob, [flat[i] for i in need])
+    where = dict(zip(need, prep.spans))
+    decode = ColumnDecode(plan, prep.ring.ptr, where.__getitem__)
     launch = DecodeLaunch([decode])
-
-    def pre(handle):
-        for dst, src, n in copies:
-            h.d2d_async(dst, src, n, handle)
-
-    job = ZstdJob(frames, pre_launch=pre, post_launch=launch.post,
-                  window=16 << 10, snappy_frames=snappy,
-                  deflate_frames=deflate, lz4_frames=lz4)
-    return job, PendingColumns(decode, launch, ring)
+    job = DecompressJob(prep.streams, pre_launch=prep.queue_copies,
+                        post_launch=launch.post, window=16 << 10)
+    return job, PendingColumns(decode, launch, prep.ring)
 
 
 def decode_columns_gpu(blob, columns=None) -> Columns:
@@ -1167,10 +1141,8 @@ def decode_columns_gpu(blob, columns=None) -> Columns:
     .skipped; a tuple of names makes an unsupported one a ValueError,
     raised before anything is launched.  A page the kernel rejects
     raises IOError naming column, row group, page and status."""
+    from .compress import check_results
+
     job, pending = launch_columns_gpu(blob, columns)
-    results = (job.wait() + job.snappy_results + job.deflate_results
-               + job.lz4_results)
-    bad = [(i, r) for i, r in enumerate(results) if not r.ok]
-    if bad:
-        raise IOError(f"GPU page decompress failed: {bad[:3]}")
+    check_results(job.wait())
     return pending.finish()

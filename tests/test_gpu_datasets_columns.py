@@ -14,7 +14,14 @@ from helpers import Stack  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _write_shards(d, n_shards=2, rows=1500):
+# shard 2 mixes codecs by column, so a coalesced launch of the three
+# holds streams of all four codecs, at non-zero offsets in its lists
+_SHARD_CODECS = ["snappy", "zstd",
+                 {"ids": "gzip", "toks.list.element": "lz4",
+                  "text": "zstd"}]
+
+
+def _write_shards(d, n_shards=3, rows=1500):
     d.mkdir()
     files = {}
     for s in range(n_shards):
@@ -29,7 +36,7 @@ def _write_shards(d, n_shards=2, rows=1500):
         })
         name = f"train-{s:05d}-of-{n_shards:05d}.parquet"
         path = str(d / name)
-        pq.write_table(table, path, compression="zstd" if s else "snappy",
+        pq.write_table(table, path, compression=_SHARD_CODECS[s],
                        data_page_size=4096)
         files[name] = path
     return files

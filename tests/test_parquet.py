@@ -98,14 +98,14 @@ def test_uncompressed_parquet_pages(tmp_path):
 
 def _page_plain(raw, codec_name, info):
     """CPU reconstruction of one decompressed page (v1 or v2)."""
-    # parquet "lz4" pages are raw LZ4 blocks (arrow behavior), while
-    # pa.Codec("lz4") is the FRAME codec — use the raw-block one
-    c = pa.Codec("lz4_raw" if codec_name == "lz4" else codec_name)
     lvl = info.lvl_bytes
     levels = raw[info.comp_offset:info.comp_offset + lvl]
     body = raw[info.comp_offset + lvl:info.comp_offset + info.comp_size]
-    if not info.is_compressed:
+    if not info.is_compressed or codec_name == "none":
         return levels + body
+    # parquet "lz4" pages are raw LZ4 blocks (arrow behavior), while
+    # pa.Codec("lz4") is the FRAME codec — use the raw-block one
+    c = pa.Codec("lz4_raw" if codec_name == "lz4" else codec_name)
     return levels + bytes(c.decompress(body, info.uncomp_size - lvl))
 
 
@@ -158,3 +158,84 @@ def test_gpu_page_decompress(tmp_path, codec, page_version):
     for (off, sz), (_, info) in zip(spans, pages):
         want = _page_plain(raw, codec, info)
         assert bytes(out[off:off + sz]) == want
+
+
+def _write_mixed(path, page_version, n_rows=3000):
+    """One file whose column chunks use every page codec the GPU path
+    has, and an uncompressed one."""
+    import numpy as np
+
+    rng = np.random.default_rng(5)
+    words = [f"tok{i}" for i in range(500)]
+    text = [" ".join(words[j] for j in rng.integers(0, 500, size=20))
+            for _ in range(n_rows)]
+    table = pa.table({
+        "a": text,
+        "b": [t[::-1] for t in text],
+        "c": np.arange(n_rows, dtype=np.int64),
+        "d": rng.random(n_rows),
+        "e": np.arange(n_rows, dtype=np.int32),
+    })
+    pq.write_table(table, path,
+                   compression={"a": "zstd", "b": "snappy", "c": "gzip",
+                                "d": "lz4", "e": "none"},
+                   data_page_size=4096, write_batch_size=64,
+                   use_dictionary=False, data_page_version=page_version)
+
+
+_CODEC_NAMES = {pqf.CODEC_ZSTD: "zstd", pqf.CODEC_SNAPPY: "snappy",
+                pqf.CODEC_GZIP: "gzip", pqf.CODEC_LZ4: "lz4",
+                pqf.CODEC_LZ4_RAW: "lz4", pqf.CODEC_UNCOMPRESSED: "none"}
+
+
+def test_mixed_codec_file_has_every_codec(tmp_path):
+    from collections import Counter
+
+    p = tmp_path / "m.parquet"
+    _write_mixed(str(p), "1.0")
+    _, pages = pqf.file_pages(str(p))
+    per = Counter(_CODEC_NAMES[codec] for codec, _ in pages)
+    assert set(per) == {"zstd", "snappy", "gzip", "lz4", "none"}
+    # several streams per kernel, so descriptor indexing matters
+    assert min(per[c] for c in ("zstd", "snappy", "gzip", "lz4")) > 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("page_version", ["1.0", "2.0"])
+def test_gpu_page_decompress_all_codecs_one_job(tmp_path, page_version):
+    """zstd, snappy, gzip, lz4 and uncompressed pages of ONE file go
+    through one decompression job; every page must come back as its own
+    chunk's codec decodes it on the CPU."""
+    import ctypes
+
+    from demodel_amd.engine.pipeline import Lander
+    from demodel_amd.gpu import have_gpu, hip
+
+    assert have_gpu()
+    p = tmp_path / "m.parquet"
+    _write_mixed(str(p), page_version)
+    raw, pages = pqf.file_pages(str(p))
+
+    pos = [0]
+
+    def fill(view):
+        n = min(len(view), len(raw) - pos[0])
+        view[:n] = raw[pos[0]:pos[0] + n]
+        pos[0] += n
+        return n
+
+    lander = Lander(slab_bytes=4 << 20, n_slabs=2)
+    blob = lander.land(fill, len(raw))
+    ring, spans = pqf.decompress_pages_gpu(blob, pages)
+
+    h = hip()
+    s = h.Stream(0)
+    total = sum(sz for _, sz in spans)
+    out = bytearray(total)
+    addr = ctypes.addressof((ctypes.c_char * total).from_buffer(out))
+    h.d2h_async(addr, ring.ptr, total, s.handle)
+    s.sync()
+    assert len(spans) == len(pages)
+    for i, ((off, sz), (codec, info)) in enumerate(zip(spans, pages)):
+        want = _page_plain(raw, _CODEC_NAMES[codec], info)
+        assert bytes(out[off:off + sz]) == want, (i, _CODEC_NAMES[codec])
